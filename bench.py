@@ -27,8 +27,6 @@ Prints ONE JSON line on rank 0 (contract in the task statement), with
                          samples/s without and with the RCCL gather, interleaved rounds (a 1-rank communicator at N = 1)
   parity_vs_oracle       the gate every line is printed behind: two utterances of the TIMED output against the oracle
                          (<= 1e-4 RMS abs, <= 1e-5 rel) -- a miss is SystemExit, not a field
-  hip_hw_queues          GPU_MAX_HW_QUEUES of the process (set to 8 here before the HIP runtime loads: see below; since round 6 the
-                         default launch layout has no second stream and does not depend on it)
   ms_per_step_events     the same K timed steps measured with HIP events on the launch stream, beside the wall clock
   cpu_baseline           the numpy oracle (oracle/ddsp_oracle.py, a port of the reference algorithm) timed
                          on this host's cores over a bounded sample of the same workload (N=1 only); kind "reference" -- the
@@ -48,14 +46,6 @@ import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-
-# BEFORE the HIP runtime is loaded (import torch): eight hardware queues instead of the runtime's default four.  HIP maps
-# streams onto its hardware queues round robin; a process that holds an RCCL communicator (every rank of --gpus N, the cfg-4
-# line) has created ~7 streams before the synthesiser makes its second one, which then lands on the SAME hardware queue as the
-# caller's stream: the two-stream layout runs in one queue and the B = 32 step takes 0.359 ms instead of 0.325 (same box,
-# profiles/r05_v5_pg_fix.txt; with eight queues 0.326 with and without the communicator; every 1-rank "gather" line of rounds
-# 2 - 4 carried this +10 %).  A user's setting wins.  INTEGRATION.md, "processes that hold an RCCL communicator".
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 import numpy as np
 import torch
@@ -348,6 +338,29 @@ def build_step(model, B, F, n, device, seed, fir_impl=0):
         return synth.sins_synth(f0, st, ctrls[0], ctrls[1], ctrls[2], noise, SR, HOP,
                                 want_components=False, fir_impl=fir_impl)[0]
     return step, {"f0": f0, "ctrls": ctrls, "noise": noise, "sizes": sizes, "window": window, "win": win}
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(dirpath, arrays, seed=0):
+    """``--dump-outputs``: write each float tensor of ``arrays`` ({name: [B, ...] tensor}) as ``dirpath/<name>.npy`` in float32, at
+    most DUMP_LIMIT_BYTES in all.  Over the limit every array keeps the same fixed, seeded sample of rows (sorted), whose indices go
+    to ``<name>_rows.npy`` (float64): runs with the same arguments write the same rows, so two builds compare output for output."""
+    os.makedirs(dirpath, exist_ok=True)
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(v.nbytes for v in host.values())
+    written = {}
+    for name, v in host.items():
+        if total > DUMP_LIMIT_BYTES and v.ndim >= 1 and v.shape[0] > 1:
+            keep = max(1, int(v.shape[0] * (DUMP_LIMIT_BYTES - 2 ** 20) // total))         # headers and row indices fit too
+            rows = np.sort(np.random.default_rng(seed).choice(v.shape[0], size=keep, replace=False))
+            v = np.ascontiguousarray(v[rows])
+            np.save(os.path.join(dirpath, name + "_rows.npy"), rows.astype(np.float64))
+            written[name + "_rows"] = [int(keep)]
+        np.save(os.path.join(dirpath, name + ".npy"), v.astype(np.float32))
+        written[name] = list(v.shape)
+    return written
 
 
 def time_steps(step, steps, warmup, fence):
@@ -1616,7 +1629,12 @@ def main(argv=None):
     ap.add_argument("--no-cfg4-gather", action="store_true", help="cfg-4 line without opening a 1-rank communicator at N = 1")
     ap.add_argument("--no-parity-gate", action="store_true",
                     help="do not hold the timed output against the oracle before printing (A/B runs of broken ablation builds)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0's shard) as DIR/<name>.npy "
+                         "(float32, at most 64 MB in all; a fixed seeded sample of rows beyond that)")
     a = ap.parse_args(argv)
+    if a.dump_outputs and a.model not in ("combsub", "sins") + FAST_MODELS:
+        ap.error("--dump-outputs: --model %s is not supported (combsub, sins, %s)" % (a.model, ", ".join(FAST_MODELS)))
     if a.only_steps:
         a.prewarm_seconds = 0.0
 
@@ -1668,6 +1686,8 @@ def main(argv=None):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed, events_ms = float(tt[0].item()), float(tt[1].item())
     assert torch.isfinite(out).all()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"signal": out})
 
     gather_ms = None
     if a.gather:                                     # world 1: a 1-rank RCCL communicator, the same call path
@@ -1783,7 +1803,6 @@ def main(argv=None):
             "value": value, "unit": "samples/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "prewarm_s": a.prewarm_seconds,
             "ms_per_step": ms, "ms_per_step_events": events_ms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f32", "data": "synthetic",
-            "hip_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"),
             "config": {"workload": "%s B=%d/GPU x %.0f s utterances (F=%d, T=%d), n_mag %d/%d/%d, sr 44100, hop 512, "
                                    "DSP path (HOT-1 + HOT-2) from resident f0 / raw controls ~N(0,1) / uniform noise, "
                                    "signal only" % (a.model, B, a.seconds, F, T, n, n, n),

@@ -749,7 +749,7 @@ int combsub_rows(const TailCall& a, SynthWs& w, hipStream_t st, void* aux_stream
   // two streams 0.319: what the overlap wins, three cross-stream hand-overs of ~7 us lose), while every separate launch pays its
   // own ramp and drain: the four front kernels 107.6 us one after the other, 81 as one launch; the two independent filters 145 /
   // 125.  [MI355X] same box, B = 32 x 10 s: 0.3194 -> 0.3015 ms (profiles/r06_v8_*, r06_v9_*).  The second stream, its events and
-  // the hardware-queue question of round 5 (GPU_MAX_HW_QUEUES) are gone from this path.
+  // the hardware-queue question of round 5 are gone from this path.
   // Same kernels, same arguments as the layouts below (same bits below 4096 frames: tests/test_small_shapes.py; above, the paired
   // filters' run split differs: rounding-level); knob SMALL_PATH = 1: never; knob STREAM_LAYOUT = 1 / 4: not at batch shapes.
   if (w.taps3 && fused_shape_ok(R, F, hop, n_ap, n_harm, n_nz, a.fir_impl, a.gen.on != 0, true)) {

@@ -25,6 +25,10 @@ Fixtures (all float32 unless noted):
   filter_n{128,257,512}.npz, combsub_mixed.npz, sins_mixed.npz   tap synthesis, filters and tails at the larger bin counts
   *_grad.npz        autograd of Sins / CombSub / CombSubFast / CombSubSuperFast.forward w.r.t. the controls Unit2Control produced,
                     for a random cotangent R: d(sum(signal * R)) / d ctrl
+  reftest_*.npz     what three tests once computed from the reference at run time (--reference-tests regenerates these alone):
+                    sinesrc_module (SourceModuleHnNSF's state_dict and output, tests/test_sine_source.py), fir_autograd
+                    (ddsp.core.fft_convolve's autograd, tests/test_backward_fir.py), mel_stft_class (STFT.get_mel,
+                    tests/test_mel.py); the inputs are re-drawn from the same seeds by the tests
 """
 import os
 import sys
@@ -302,6 +306,55 @@ def mel_shifted_fixtures():
         print(f, os.path.getsize(os.path.join(HERE, f)))
 
 
+def reference_test_fixtures():
+    """reftest_*.npz: the reference-side results of test_sine_source.py::test_against_reference_source_module,
+    test_backward_fir.py::test_oracle_backward_against_reference_autograd and test_mel.py::test_against_reference_stft_class,
+    on the inputs those tests draw (same seeds, same calls)."""
+    from oracle import ddsp_oracle as O
+    core, _ = import_reference()
+    import nsf_hifigan.models as nm
+    import nsf_hifigan.nvSTFT as nv
+    sr, upp = 44100, 512
+    # SourceModuleHnNSF (models.py:140-204), its two random draws injected
+    torch.manual_seed(5)
+    ref = nm.SourceModuleHnNSF(sr, harmonic_num=8)
+    f0 = torch.from_numpy(O.synth_f0(2, 12, sr, upp, seed=6)[..., 0]).clone()
+    f0[0, 3:5] = 0
+    ri = torch.rand(1, 1, 9, generator=torch.Generator().manual_seed(7))
+    nz = torch.randn(2, 12 * upp, 9, generator=torch.Generator().manual_seed(8))
+    with mock.patch("torch.rand", side_effect=lambda *a, **k: ri.clone()), \
+            mock.patch("torch.randn_like", side_effect=lambda t: nz), \
+            mock.patch("torch.randn", side_effect=lambda *a, **k: nz), torch.no_grad():
+        want = ref(f0, upp)
+    out = {"sd:" + k: v.numpy() for k, v in ref.state_dict().items()}
+    out["want"] = want.numpy()
+    np.savez_compressed(os.path.join(HERE, "reftest_sinesrc_module.npz"), **out)
+    # ddsp.core.fft_convolve under autograd (core.py:120-182): d(sum(conv(x, ir) * R)) / dx, / dir
+    conv = getattr(core, "_reference_fft_convolve", core.fft_convolve)
+    out = {}
+    for B, F, N in ((2, 7, 510), (1, 4, 30), (1, 1, 510)):
+        rng = np.random.default_rng(10 * F + N)                     # tests/test_backward_fir.py::_case
+        x = (rng.random((B, F * 512)) * 2 - 1).astype(np.float32)
+        ir = (rng.standard_normal((B, F, N)) / np.sqrt(N) * rng.uniform(0.05, 2.0, size=(B, F, 1))).astype(np.float32)
+        R = rng.standard_normal((B, F * 512)).astype(np.float32)
+        a = torch.from_numpy(x).requires_grad_(True)
+        h = torch.from_numpy(ir).requires_grad_(True)
+        (conv(a, h) * torch.from_numpy(R)).sum().backward()
+        out["dx_%d_%d_%d" % (B, F, N)] = a.grad.numpy()
+        out["dh_%d_%d_%d" % (B, F, N)] = h.grad.numpy()
+    np.savez_compressed(os.path.join(HERE, "reftest_fir_autograd.npz"), **out)
+    # nvSTFT.STFT.get_mel (nvSTFT.py:73-117) with the oracle's Slaney filterbank injected
+    basis = O.mel_filterbank_slaney(44100, 2048, 128, 40, 16000)
+    g = torch.Generator().manual_seed(3)
+    y = torch.randn(2, 512 * 12, generator=g) * 0.2
+    with mock.patch.object(nv, "librosa_mel_fn", side_effect=lambda **kw: basis):
+        ref = nv.STFT(44100, 128, 2048, 2048, 512, 40, 16000).get_mel(y)
+        ref_shift = nv.STFT(44100, 128, 2048, 2048, 512, 40, 16000).get_mel(y, keyshift=-1.5, speed=1.1, center=True)
+    np.savez_compressed(os.path.join(HERE, "reftest_mel_stft_class.npz"), ref=ref.numpy(), ref_shift=ref_shift.numpy())
+    for f in ("reftest_sinesrc_module.npz", "reftest_fir_autograd.npz", "reftest_mel_stft_class.npz"):
+        print(f, os.path.getsize(os.path.join(HERE, f)))
+
+
 def main():
     from oracle import ddsp_oracle as O
     if "--only-loss" in sys.argv:
@@ -310,6 +363,8 @@ def main():
         return mel_shifted_fixtures()
     if "--baseline-shapes" in sys.argv:
         return baseline_shape_fixtures()
+    if "--reference-tests" in sys.argv:
+        return reference_test_fixtures()
     core, V = import_reference()
     torch.manual_seed(0)
     sr, hop = 44100, 512

@@ -26,22 +26,16 @@ def _case(B, F, N, seed):
     return x, ir, R
 
 
-def test_oracle_backward_against_reference_autograd():
-    ref_root = os.environ.get("DDSP_REFERENCE_PATH", "/root/reference")
-    if not os.path.isdir(os.path.join(ref_root, "ddsp")):
-        pytest.skip("reference checkout not present (only in the build container)")
-    if ref_root not in sys.path:
-        sys.path.insert(0, ref_root)
-    import ddsp.core as rcore
-    conv = getattr(rcore, "_reference_fft_convolve", rcore.fft_convolve)
+def test_oracle_backward_against_reference_autograd(golden_dir):
+    """the oracle's adjoint against the reference's autograd through ddsp.core.fft_convolve (fixture reftest_fir_autograd.npz:
+    tests/golden/make_golden.py --reference-tests, on the inputs _case draws here)"""
+    g = np.load(os.path.join(golden_dir, "reftest_fir_autograd.npz"))
     for B, F, N in ((2, 7, 510), (1, 4, 30), (1, 1, 510)):
         x, ir, R = _case(B, F, N, 10 * F + N)
-        a = torch.from_numpy(x).requires_grad_(True)
-        h = torch.from_numpy(ir).requires_grad_(True)
-        (conv(a, h) * torch.from_numpy(R)).sum().backward()
+        ref_dx, ref_dh = g["dx_%d_%d_%d" % (B, F, N)], g["dh_%d_%d_%d" % (B, F, N)]
         dx, dh = O.ltv_fir_backward(R, x, ir)
-        assert rms(dx - a.grad.numpy()) <= 2e-6 * rms(dx)
-        assert rms(dh - h.grad.numpy()) <= 2e-6 * rms(dh)
+        assert rms(dx - ref_dx) <= 2e-6 * rms(dx)
+        assert rms(dh - ref_dh) <= 2e-6 * rms(dh)
 
 
 @pytest.mark.parametrize("dev", BACKENDS, indirect=True)

@@ -237,25 +237,14 @@ def test_get_mel_contract(dev):
 
 
 @pytest.mark.parametrize("dev", BACKENDS, indirect=True)
-def test_against_reference_stft_class(dev):
-    """the reference's own STFT.get_mel (librosa's filterbank replaced by the oracle's, the only missing piece in this
-    image) against the drop-in on the same audio"""
-    ref_root = os.environ.get("DDSP_REFERENCE_PATH", "/root/reference")
-    if not os.path.isdir(os.path.join(ref_root, "nsf_hifigan")):
-        pytest.skip("reference checkout not present (only in the build container)")
-    if ref_root not in sys.path:
-        sys.path.insert(0, ref_root)
-    for name in ["librosa", "librosa.util", "librosa.filters", "librosa.core", "librosa.sequence", "soundfile", "torchaudio",
-                 "torchaudio.transforms"]:
-        sys.modules.setdefault(name, MagicMock())
-    import nsf_hifigan.nvSTFT as nv
+def test_against_reference_stft_class(dev, golden_dir):
+    """the reference's own STFT.get_mel (librosa's filterbank replaced by the oracle's; fixture reftest_mel_stft_class.npz:
+    tests/golden/make_golden.py --reference-tests) against the drop-in on the same audio"""
     from ddsp_svc_amd import mel as M
-    basis = O.mel_filterbank_slaney(44100, 2048, 128, 40, 16000)
+    fx = np.load(os.path.join(golden_dir, "reftest_mel_stft_class.npz"))
     g = torch.Generator().manual_seed(3)
     y = torch.randn(2, 512 * 12, generator=g) * 0.2
-    with mock.patch.object(nv, "librosa_mel_fn", side_effect=lambda **kw: basis):
-        ref = nv.STFT(44100, 128, 2048, 2048, 512, 40, 16000).get_mel(y)
-        ref_shift = nv.STFT(44100, 128, 2048, 2048, 512, 40, 16000).get_mel(y, keyshift=-1.5, speed=1.1, center=True)
+    ref, ref_shift = torch.from_numpy(fx["ref"]), torch.from_numpy(fx["ref_shift"])
     ours = M.STFT(44100, 128, 2048, 2048, 512, 40, 16000).get_mel(y.to(dev)).cpu()
     assert ours.shape == ref.shape
     _check(ours.numpy(), ref.numpy())

@@ -231,10 +231,9 @@ def test_one_rank_rccl_logical_shards_gpu():
 @pytest.mark.gpu
 def test_a_live_rccl_communicator_does_not_slow_the_step_gpu():
     """Rounds 2 - 5: a process that had opened an RCCL communicator (every rank of a multi-GPU job) ran the B = 32 step ~10 % slower
-    unless GPU_MAX_HW_QUEUES=8 was exported before HIP loaded -- the communicator's streams pushed the synthesiser's SECOND stream onto
-    the caller's hardware queue (EXPERIMENTS 5.3).  Round 6's default layout of a 256-bin step issues everything on the caller's stream
-    (no second stream, no events), and the package sets the variable when it is imported before the runtime initialises: the step
-    time with a live 1-rank communicator, default environment, stays within 5 % of the time without one (same process, same box)."""
+    -- the communicator's streams pushed the synthesiser's SECOND stream onto the caller's hardware queue (EXPERIMENTS 5.3).  Round 6's
+    default layout of a 256-bin step issues everything on the caller's stream (no second stream, no events): the step time with a
+    live 1-rank communicator, default environment, stays within 5 % of the time without one (same process, same box)."""
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     import time

@@ -83,29 +83,18 @@ def test_source_module_dropin(dev, monkeypatch):
 
 
 @pytest.mark.parametrize("dev", BACKENDS, indirect=True)
-def test_against_reference_source_module(dev):
-    ref_root = os.environ.get("DDSP_REFERENCE_PATH", "/root/reference")
-    if not os.path.isdir(os.path.join(ref_root, "nsf_hifigan")):
-        pytest.skip("reference checkout not present (only in the build container)")
-    if ref_root not in sys.path:
-        sys.path.insert(0, ref_root)
-    for name in ["librosa", "librosa.util", "librosa.filters", "librosa.core", "librosa.sequence", "soundfile", "torchaudio",
-                 "torchaudio.transforms"]:
-        sys.modules.setdefault(name, MagicMock())
-    import nsf_hifigan.models as nm
+def test_against_reference_source_module(dev, golden_dir):
+    """the drop-in with the reference module's weights (strict state_dict load) against the reference's CPU output on the same
+    f0 and injected draws (fixture reftest_sinesrc_module.npz: tests/golden/make_golden.py --reference-tests)"""
     from ddsp_svc_amd import nsf_source as S
-    torch.manual_seed(5)
-    ref = nm.SourceModuleHnNSF(SR, harmonic_num=8)
+    g = np.load(os.path.join(golden_dir, "reftest_sinesrc_module.npz"))
     ours = S.SourceModuleHnNSF(SR, harmonic_num=8)
-    ours.load_state_dict(ref.state_dict(), strict=True)
+    ours.load_state_dict({k[3:]: torch.from_numpy(g[k]) for k in g.files if k.startswith("sd:")}, strict=True)
     f0 = torch.from_numpy(O.synth_f0(2, 12, SR, UPP, seed=6)[..., 0]).clone()
     f0[0, 3:5] = 0
     ri = torch.rand(1, 1, 9, generator=torch.Generator().manual_seed(7))
     nz = torch.randn(2, 12 * UPP, 9, generator=torch.Generator().manual_seed(8))
-    with mock.patch("torch.rand", side_effect=lambda *a, **k: ri.clone()), \
-            mock.patch("torch.randn_like", side_effect=lambda t: nz), \
-            mock.patch("torch.randn", side_effect=lambda *a, **k: nz), torch.no_grad():
-        want = ref(f0, UPP)                                  # the reference on its CPU path
+    want = torch.from_numpy(g["want"])                   # the reference on its CPU path
     ours = ours.to(dev)
     rid, nzd = ri.to(dev), nz.to(dev)
     with mock.patch("torch.rand", side_effect=lambda *a, **k: rid.clone()), \
