@@ -86,6 +86,9 @@ SIGNATURES = {
     "ddsp_hip_mel_frames": (c_int, [c_int, c_int, c_int]),
     "ddsp_hip_mel_spectrogram": (c_int, [P, c_int, c_int, P, c_int, c_int, P, P, P, c_int, c_int, c_float, P,
                                          c_long, c_long, c_long, P]),
+    "ddsp_hip_mel_backward_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "ddsp_hip_mel_spectrogram_backward": (c_int, [P, c_int, c_int, P, c_int, c_int, P, P, P, c_int, P, c_int, c_float, P,
+                                                  c_long, c_long, c_long, P, P, c_size_t, P]),
     "ddsp_hip_mel_shifted_table_bytes": (c_size_t, [c_int, c_int]),
     "ddsp_hip_mel_shifted_tables": (c_int, [c_int, c_int, c_int, P, P]),
     "ddsp_hip_mel_shifted_frames": (c_int, [c_int, c_int, c_int, c_int, c_int]),

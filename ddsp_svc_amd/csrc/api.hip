@@ -1153,6 +1153,26 @@ int ddsp_hip_mel_spectrogram(const float* audio, int B, int T, const float* wind
   return finish();
 }
 
+size_t ddsp_hip_mel_backward_workspace_bytes(int B, int T, int n_fft, int hop) { return mel_bwd_ws_bytes(B, T, n_fft, hop); }
+
+int ddsp_hip_mel_spectrogram_backward(const float* audio, int B, int T, const float* window, int n_fft, int hop,
+                                      const float* mel_basis, const int* band, const float* band_weights,
+                                      int n_band_weights, const int* bin_filters, int n_mels, float clip_val,
+                                      const float* grad_out, long stride_b, long stride_mel, long stride_frame,
+                                      float* grad_audio, void* ws, size_t ws_bytes, void* stream) {
+  if (B < 0 || T < 1 || n_fft < 2 || hop < 1 || hop > n_fft || n_mels < 1) return DDSP_HIP_EINVAL;
+  if (B == 0) return 0;
+  if (!audio || !window || !mel_basis || !band || !bin_filters || !grad_out || !grad_audio) return DDSP_HIP_EINVAL;
+  const size_t need = mel_bwd_ws_bytes(B, T, n_fft, hop);
+  if (need == 0 || B > 65535 || n_mels > 1016) return DDSP_HIP_ESHAPE;
+  if (!ws || ws_bytes < need) return DDSP_HIP_EWS;
+  if (launch_mel_bwd(audio, B, T, window, n_fft, hop, mel_basis, band, band_weights, n_band_weights, bin_filters, n_mels,
+                     clip_val, grad_out, stride_b, stride_mel, stride_frame, grad_audio, static_cast<float*>(ws), ws_bytes,
+                     S(stream)) != 0)
+    return DDSP_HIP_ESHAPE;
+  return finish();
+}
+
 size_t ddsp_hip_mel_shifted_table_bytes(int n_fft_new, int n_bins) { return mel_czt_table_bytes(n_fft_new, n_bins); }
 
 int ddsp_hip_mel_shifted_tables(int n_fft_new, int win_new, int n_bins, float* tables, void* stream) {

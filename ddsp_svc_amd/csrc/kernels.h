@@ -139,6 +139,11 @@ int launch_mel(const float* audio, int B, int T, const float* window, int n_fft,
                const int* band, const float* packed, int packed_len, int n_mels, float clip, float* out, long sb,
                long sm, long sf, hipStream_t st);
 int mel_frames(int T, int n_fft, int hop);
+// its adjoint w.r.t. the waveform (mel.hip): per-frame gradients in ws ([B][frames][2048] floats), gathered per sample
+size_t mel_bwd_ws_bytes(int B, int T, int n_fft, int hop);
+int launch_mel_bwd(const float* audio, int B, int T, const float* window, int n_fft, int hop, const float* basis,
+                   const int* band, const float* packed, int packed_len, const int* bins, int n_mels, float clip,
+                   const float* gout, long sb, long sm, long sf, float* dx, float* ws, size_t ws_bytes, hipStream_t st);
 // the same front-end at any transform length / hop / centring (mel_czt.hip; nvSTFT.py:83-85,109-114)
 int mel_czt_plan(int n_new, int n_bins);
 size_t mel_czt_table_bytes(int n_new, int n_bins);

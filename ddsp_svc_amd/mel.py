@@ -15,6 +15,7 @@ algorithm, ``htk=False``, ``norm='slaney'``).
 import math
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _ffi
 from ._ffi import ptr
@@ -62,10 +63,75 @@ def _bands(basis):
     return table, packed
 
 
-def mel_spectrogram(audio, window, mel_basis, band, hop_length, clip_val=1e-5):
-    band, packed = band
+def _bin_filters(basis):
+    """Bin -> filter table of a mel basis for the backward's transposed projection: int32 ``[n_bins + 1 + nnz]`` = the
+    offsets of each bin's entries, then the ids of the filters whose band (``_bands``) holds the bin, ascending per bin."""
+    n_mels, n_bins = basis.shape
+    nz = basis != 0
+    idx = torch.arange(n_bins, device=basis.device)
+    lo = torch.where(nz, idx, n_bins).min(dim=1).values
+    hi = torch.where(nz, idx + 1, 0).max(dim=1).values
+    inband = (idx[None, :] >= lo[:, None]) & (idx[None, :] < hi[:, None])      # all-zero rows: lo = n_bins, hi = 0, empty
+    pairs = torch.nonzero(inband.t())                                           # (bin, filter), bin-major, filters ascending
+    counts = inband.sum(dim=0)
+    offsets = torch.cat([torch.zeros(1, dtype=counts.dtype, device=basis.device), torch.cumsum(counts, 0)])
+    return torch.cat([offsets, pairs[:, 1]]).to(torch.int32).contiguous()
+
+
+def _needs_grad(y):
+    return torch.is_grad_enabled() and getattr(y, "requires_grad", False)
+
+
+class _MelSpectrogram(torch.autograd.Function):
+    """``mel_spectrogram`` with its adjoint w.r.t. the waveform (csrc/mel.hip, k_mel_bwd + k_mel_bwd_gather).  The basis and
+    the window are constants, as the reference's buffers are."""
+
+    @staticmethod
+    def forward(ctx, audio, window, mel_basis, band, packed, bins, hop_length, clip_val):
+        a = audio if (audio.dtype == torch.float32 and audio.is_contiguous()) else audio.float().contiguous()
+        out = _mel_forward(a, window, mel_basis, (band, packed), hop_length, clip_val)
+        ctx.save_for_backward(a, window, mel_basis, band, packed, bins)
+        ctx.hop, ctx.clip, ctx.dtype = int(hop_length), float(clip_val), audio.dtype
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        a, window, mel_basis, band, packed, bins = ctx.saved_tensors
+        g = grad if grad.dtype == torch.float32 else grad.float()
+        _ffi.check_device(g)
+        B, T = a.shape
+        n_fft = window.numel()
+        lib = _ffi.lib()
+        nbytes = lib.ddsp_hip_mel_backward_workspace_bytes(B, T, n_fft, ctx.hop)
+        if nbytes == 0:
+            raise RuntimeError("get_mel backward: n_fft %d, hop %d is outside the kernel's configuration (2048, 512)"
+                               % (n_fft, ctx.hop))
+        ws = torch.empty(nbytes // 4, dtype=torch.float32, device=a.device)
+        dx = torch.empty(B, T, dtype=torch.float32, device=a.device)
+        _ffi.check(lib.ddsp_hip_mel_spectrogram_backward(ptr(a), B, T, ptr(window), n_fft, ctx.hop, ptr(mel_basis), ptr(band),
+                                                         ptr(packed), packed.numel(), ptr(bins), mel_basis.shape[0], ctx.clip,
+                                                         ptr(g), g.stride(0), g.stride(1), g.stride(2), ptr(dx), ptr(ws),
+                                                         nbytes, _ffi.stream_of(a)))
+        return dx.to(ctx.dtype), None, None, None, None, None, None, None
+
+
+def mel_spectrogram(audio, window, mel_basis, band, hop_length, clip_val=1e-5, bins=None):
     """``[B,T]`` waveform -> ``[B, n_mels, frames]`` log-mel (nvSTFT.py:97-116).  The result is laid out
-    frame-major in memory, so the ``transpose(1, 2)`` every caller applies (diffusion/vocoder.py:147) is free."""
+    frame-major in memory, so the ``transpose(1, 2)`` every caller applies (diffusion/vocoder.py:147) is free.
+    When ``audio`` requires a gradient (and grad mode is on) the result carries an autograd node whose backward is the
+    HIP adjoint; ``bins``: ``_bin_filters(mel_basis)``, built here when not given."""
+    if _needs_grad(audio):
+        band_t, packed = band
+        if bins is None:
+            bins = _bin_filters(mel_basis)
+        _ffi.check_device(audio, window, mel_basis, band_t, packed, bins)
+        return _MelSpectrogram.apply(audio, window, mel_basis, band_t, packed, bins, hop_length, clip_val)
+    return _mel_forward(audio, window, mel_basis, band, hop_length, clip_val)
+
+
+def _mel_forward(audio, window, mel_basis, band, hop_length, clip_val):
+    band, packed = band
     _ffi.check_device(audio, window, mel_basis, band, packed)
     if audio.dim() != 2:
         raise ValueError("audio must be [B, T]")
@@ -141,6 +207,7 @@ class STFT:
         self.mel_basis = {}
         self.hann_window = {}
         self._band = {}
+        self._bins = {}
         self._shifted = {}
         self._given_basis = mel_basis
 
@@ -158,9 +225,22 @@ class STFT:
         return self.mel_basis[key], self._band[key], self.hann_window[wkey]
 
     def get_mel(self, y, keyshift=0, speed=1, center=False):
+        """Differentiable w.r.t. ``y`` in the plain configuration (keyshift 0, speed 1, center False, n_fft = win_size =
+        2048, hop_length 512); a call elsewhere that needs a gradient raises instead of returning a detached result."""
         basis, band, window = self._tables(y.device)
         if (keyshift == 0 and speed == 1 and not center and self.n_fft == self.win_size == 2048 and self.hop_length == 512):
-            return mel_spectrogram(y, window, basis, band, self.hop_length, self.clip_val)
+            bins = None
+            if _needs_grad(y):
+                key = str(self.fmax) + "_" + str(y.device)
+                if key not in self._bins:
+                    self._bins[key] = _bin_filters(basis)
+                bins = self._bins[key]
+            return mel_spectrogram(y, window, basis, band, self.hop_length, self.clip_val, bins=bins)
+        if _needs_grad(y):
+            raise RuntimeError("get_mel: the gradient w.r.t. the waveform is implemented for keyshift=0, speed=1, center=False, "
+                               "n_fft = win_size = 2048, hop_length = 512 only (this call: keyshift %s, speed %s, center %s, "
+                               "n_fft %d, win_size %d, hop_length %d)" % (keyshift, speed, center, self.n_fft, self.win_size,
+                                                                          self.hop_length))
         return _get_mel_shifted(self, y, keyshift, speed, center, band, self._shifted)
 
 
@@ -187,7 +267,9 @@ def patch_reference_stft():
     """Route ``nsf_hifigan.nvSTFT.STFT.get_mel`` of an importable reference checkout through the HIP kernels for every
     call on a ``[B, T]`` GPU tensor the kernels take (the cascade's configuration on csrc/mel.hip; keyshift / speed /
     center / other sizes on csrc/mel_czt.hip); CPU tensors and sizes outside the kernels' range keep the reference
-    code.  The reference's own mel basis (librosa) is used as it is."""
+    code.  The reference's own mel basis (librosa) is used as it is.  A call that needs a gradient w.r.t. ``y`` (the
+    cascades' DDSP loss) takes the HIP autograd node in the plain configuration on the GPU and the reference's
+    differentiable torch code everywhere else."""
     import nsf_hifigan.nvSTFT as nv
     if hasattr(nv.STFT, "_reference_get_mel"):
         return nv
@@ -197,8 +279,9 @@ def patch_reference_stft():
     def get_mel(self, y, keyshift=0, speed=1, center=False):
         plain = (keyshift == 0 and speed == 1 and not center and self.n_fft == 2048 and self.win_size == 2048 and
                  self.hop_length == 512)
+        grad = _needs_grad(y)
         hip_ok = (getattr(y, "is_cuda", False) and y.dim() == 2 and
-                  (plain or _shifted_in_range(self.n_fft, self.win_size, self.hop_length, keyshift, speed)))
+                  (plain or (not grad and _shifted_in_range(self.n_fft, self.win_size, self.hop_length, keyshift, speed))))
         if not hip_ok:
             return ref_get_mel(self, y, keyshift=keyshift, speed=speed, center=center)
         key = str(self.fmax) + "_" + str(y.device)
@@ -214,8 +297,14 @@ def patch_reference_stft():
             bands[key] = _bands(self.mel_basis[key])
         if not plain:
             return _get_mel_shifted(self, y, keyshift, speed, center, bands[key], self.__dict__.setdefault("_hip_shifted", {}))
+        bins = None
+        if grad:
+            tables = self.__dict__.setdefault("_hip_bins", {})
+            if key not in tables:
+                tables[key] = _bin_filters(self.mel_basis[key])
+            bins = tables[key]
         return mel_spectrogram(y, self.hann_window[wkey], self.mel_basis[key].contiguous(), bands[key],
-                               self.hop_length, self.clip_val)
+                               self.hop_length, self.clip_val, bins=bins)
 
     nv.STFT.get_mel = get_mel
     return nv

@@ -323,6 +323,21 @@ int ddsp_hip_mel_spectrogram(const float* audio, int B, int T, const float* wind
                              int n_band_weights, int n_mels, float clip_val,
                              float* out, long stride_b, long stride_mel, long stride_frame, void* stream);
 
+/* Adjoint of ddsp_hip_mel_spectrogram w.r.t. the waveform (the cascades' DDSP loss, F.mse_loss(get_mel(ddsp_wav), gt)):
+ * grad_audio[B,T] (contiguous, overwritten) = d <grad_out, log-mel> / d audio, for the cotangent element (b, mel, frame) read
+ * at grad_out[b*stride_b + mel*stride_mel + frame*stride_frame] (any strides, 0 included).  The forward's arguments
+ * otherwise; bin_filters (int32) = n_fft/2+2 offsets, then filter ids: bin k lies in the band of the filters
+ * bin_filters[n_fft/2+2 + e], e in [bin_filters[k], bin_filters[k+1]) (every row whose band holds k, ascending).
+ * ws: ddsp_hip_mel_backward_workspace_bytes(B, T, n_fft, hop) bytes (each frame's gradient; 0 for an unsupported
+ * configuration).  No atomics: the same bits on every call.  Supported: n_fft == 2048, hop == 512, n_mels <= 1016,
+ * B <= 65535 (DDSP_HIP_ESHAPE otherwise); DDSP_HIP_EWS for a short or NULL workspace. */
+size_t ddsp_hip_mel_backward_workspace_bytes(int B, int T, int n_fft, int hop);
+int ddsp_hip_mel_spectrogram_backward(const float* audio, int B, int T, const float* window, int n_fft, int hop,
+                                      const float* mel_basis, const int* band, const float* band_weights,
+                                      int n_band_weights, const int* bin_filters, int n_mels, float clip_val,
+                                      const float* grad_out, long stride_b, long stride_mel, long stride_frame,
+                                      float* grad_audio, void* ws, size_t ws_bytes, void* stream);
+
 /* STFT.get_mel(y, keyshift, speed, center) in full (nvSTFT.py:73-117; the cascade's formant shift, main_diff.py:359; the
  * pitch augmentation of preprocess.py:88-92), and any (n_fft, win, hop) configuration:
  *   n_fft_new = round(n_fft 2^(keyshift/12)), win_new = round(win 2^(keyshift/12)), hop_new = round(hop speed) (:83-85);
