@@ -146,7 +146,8 @@ def sinusoid_bank(x: np.ndarray, f0_frames: np.ndarray, amp_ctrl: np.ndarray,
 def combtooth(x: np.ndarray, f0_frames: np.ndarray, sr: float, hop: int) -> np.ndarray:
     """``sinc(sr*x/(f0+1e-3))``: z is formed in float32 (int-tensor * float32, float32 add and
     divide), and ``torch.sinc`` evaluates ``sin(fl32(pi32*z))/fl32(pi32*z)`` in float32, 1 at 0.
-    The float32 product pi*z (|z| up to ~340) is reproduced; sine/divide are float64."""
+    The float32 product pi*z is reproduced; sine/divide are float64.  Pinned to the reference over f0 = 12.5 .. 4 400 Hz, i.e.
+    |z| up to sr / (2 f0) = 1 764 (|pi z| <= 5 541 rad): tests/test_pitch_range.py, fixtures pitch_*.npz."""
     f0f = np.asarray(f0_frames, dtype=F32)
     if f0f.ndim == 2:
         f0f = f0f[:, :, None]

@@ -25,6 +25,14 @@ Fixtures (all float32 unless noted):
   filter_n{128,257,512}.npz, combsub_mixed.npz, sins_mixed.npz   tap synthesis, filters and tails at the larger bin counts
   *_grad.npz        autograd of Sins / CombSub / CombSubFast / CombSubSuperFast.forward w.r.t. the controls Unit2Control produced,
                     for a random cotangent R: d(sum(signal * R)) / d ctrl
+  pitch_*.npz       the extended pitch range key shifting reaches (12.5 .. 4 400 Hz, tests/pitch_regimes.py; --pitch-range
+                    regenerates these alone): pitch_{sins,combsub,csfast,cssuper}_{a,b}.npz are Sins / CombSub / CombSubFast /
+                    CombSubSuperFast.forward with fixed controls and injected noise, B = 3, F = 24, rows of the glide / jumps /
+                    nyquist (a) and hw_edge / floor_ceiling / 12.5 <-> 50 Hz jumps (b) regimes, controls N(0, 1) (a) or
+                    sigma 3 (b); pitch_fastsrc.npz is CombSubSuperFast.fast_source_gen on all six rows; pitch_sinesrc.npz is
+                    SourceModuleHnNSF (dim 9) on them with unvoiced frames.  Controls and noise are regenerated from seeds
+                    (checked by input_checks), waveforms stored every PITCH_DEC-th sample  vocoder.py:556-710, :735-862,
+                    models.py:140-204
   reftest_*.npz     what three tests once computed from the reference at run time (--reference-tests regenerates these alone):
                     sinesrc_module (SourceModuleHnNSF's state_dict and output, tests/test_sine_source.py), fir_autograd
                     (ddsp.core.fft_convolve's autograd, tests/test_backward_fir.py), mel_stft_class (STFT.get_mel,
@@ -138,7 +146,7 @@ class FixedControls(torch.nn.Module):
         super().__init__()
         self.ctrls = ctrls
 
-    def forward(self, units, f0, phase, volume, spk_id=None, spk_mix_dict=None):
+    def forward(self, units, f0, phase, volume, spk_id=None, spk_mix_dict=None, aug_shift=None):
         self.phase_frames = phase
         return self.ctrls, torch.zeros(units.shape[0], units.shape[1], 1)
 
@@ -355,6 +363,85 @@ def reference_test_fixtures():
         print(f, os.path.getsize(os.path.join(HERE, f)))
 
 
+from tests.pitch_regimes import PITCH_DEC, PITCH_SETS, PITCH_TAILS, pitch_inputs  # noqa: E402  (shared with the tests)
+
+
+def pitch_range_fixtures():
+    """pitch_*.npz: the four DSP tails, the CombSubSuperFast exciter and the NSF harmonic source at 12.5 .. 4 400 Hz (the f0
+    range main.py / gui.py reach with f0_min 50, f0_max 1100 and a key shift of -24 .. +24), run by the reference itself"""
+    core, V = import_reference()
+    import nsf_hifigan.models as nm
+    sr, hop = 44100, 512
+    names = {"sins": ("amplitudes", "group_delay", "noise_magnitude"),
+             "combsub": ("group_delay", "harmonic_magnitude", "noise_magnitude"),
+             "csfast": ("harmonic_magnitude", "harmonic_phase", "noise_magnitude"),
+             "cssuper": ("harmonic_magnitude", "harmonic_phase", "noise_magnitude", "noise_phase")}
+    written = []
+    for kind in PITCH_TAILS:
+        for tag in PITCH_SETS:
+            f0, sizes, ctrls, noise = pitch_inputs(tag, kind, sr, hop)
+            B, Fr = f0.shape[:2]
+            torch.manual_seed(0)
+            if kind == "sins":
+                model = V.Sins(sr, hop, *sizes, n_unit=8, n_spk=1)
+            elif kind == "combsub":
+                model = V.CombSub(sr, hop, *sizes, n_unit=8, n_spk=1)
+            elif kind == "csfast":
+                model = V.CombSubFast(sr, hop, n_unit=8, n_spk=1)
+            else:
+                model = V.CombSubSuperFast(sr, hop, 2048, n_unit=8, n_spk=1)
+            model = model.eval()
+            model.unit2ctrl = FixedControls({k: torch.from_numpy(c) for k, c in zip(names[kind], ctrls)})
+            if kind == "cssuper":
+                draw = torch.from_numpy(noise)
+                patch = mock.patch("torch.randn_like", side_effect=lambda t: draw.to(t))
+            else:
+                draw = torch.from_numpy((noise + np.float32(1)) / np.float32(2))       # exact inverse of 2u-1 on this grid
+                assert np.array_equal((draw * 2 - 1).numpy(), noise)
+                patch = mock.patch("torch.rand_like", side_effect=lambda t: draw.to(t))
+            with torch.no_grad(), patch:
+                signal, _, (harm, nz) = model(torch.zeros(B, Fr, 8), torch.from_numpy(f0), torch.zeros(B, Fr, 1), infer=True)
+            out = dict(f0_frames=f0, sizes=np.array(sizes), dec=np.int64(PITCH_DEC), noise_check=input_checks(noise),
+                       phase_frames=model.unit2ctrl.phase_frames.numpy()[..., 0], signal=signal.numpy()[:, ::PITCH_DEC])
+            for k, c in zip(names[kind], ctrls):
+                out["check_" + k] = input_checks(c)
+            if kind in ("sins", "combsub"):
+                out["harmonic"] = harm.numpy()[:, ::PITCH_DEC]
+                out["noise_out"] = nz.numpy()[:, ::PITCH_DEC]
+            name = f"pitch_{kind}_{tag}.npz"
+            np.savez_compressed(os.path.join(HERE, name), **out)
+            written.append(name)
+    # CombSubSuperFast.fast_source_gen (vocoder.py:639-651) on all six rows
+    f0 = np.concatenate([pitch_inputs(tag, "cssuper", sr, hop)[0] for tag in PITCH_SETS])
+    torch.manual_seed(0)
+    m = V.CombSubSuperFast(sr, hop, 2048, n_unit=8, n_spk=1)
+    with torch.no_grad():
+        comb, pf = m.fast_source_gen(torch.from_numpy(f0))
+    np.savez_compressed(os.path.join(HERE, "pitch_fastsrc.npz"), f0_frames=f0, combtooth=comb.numpy()[:, ::PITCH_DEC],
+                        phase_frames=pf.numpy()[..., 0], dec=np.int64(PITCH_DEC))
+    written.append("pitch_fastsrc.npz")
+    # SourceModuleHnNSF (models.py:140-204), dim 9: harmonics above Nyquist from f0 > 2 450 Hz; unvoiced frames; draws injected
+    f0s = f0[..., 0].copy()
+    f0s[0, 3:6] = 0.0
+    f0s[4, -2:] = 0.0
+    torch.manual_seed(61)
+    src = nm.SourceModuleHnNSF(sr, harmonic_num=8)
+    g = torch.Generator().manual_seed(64)
+    ri = torch.rand(1, 1, 9, generator=g)
+    nzs = torch.from_numpy(np.random.default_rng(65).standard_normal((f0s.shape[0], f0s.shape[1] * hop, 9)).astype(np.float32))
+    with mock.patch("torch.rand", side_effect=lambda *a, **k: ri.clone()), \
+            mock.patch("torch.randn_like", side_effect=lambda t: nzs), torch.no_grad():
+        merged = src(torch.from_numpy(f0s), hop)
+    ri0 = ri.clone()
+    ri0[..., 0] = 0
+    np.savez_compressed(os.path.join(HERE, "pitch_sinesrc.npz"), f0=f0s, rand_ini=ri0.numpy().reshape(-1), noise_seed=np.int64(65),
+                        noise_check=input_checks(nzs.numpy()), weight=src.l_linear.weight.detach().numpy(),
+                        bias=src.l_linear.bias.detach().numpy(), out=merged.numpy()[:, ::PITCH_DEC, 0], dec=np.int64(PITCH_DEC))
+    written.append("pitch_sinesrc.npz")
+    for f in written:
+        print(f, os.path.getsize(os.path.join(HERE, f)))
+
+
 def main():
     from oracle import ddsp_oracle as O
     if "--only-loss" in sys.argv:
@@ -365,6 +452,8 @@ def main():
         return baseline_shape_fixtures()
     if "--reference-tests" in sys.argv:
         return reference_test_fixtures()
+    if "--pitch-range" in sys.argv:
+        return pitch_range_fixtures()
     core, V = import_reference()
     torch.manual_seed(0)
     sr, hop = 44100, 512
@@ -645,6 +734,7 @@ def main():
     loss_fixture()
     baseline_shape_fixtures()
     mel_shifted_fixtures()
+    pitch_range_fixtures()
 
     for f in sorted(os.listdir(HERE)):
         if f.endswith(".npz"):
