@@ -12,7 +12,13 @@ data-path collective ("weak" scaling: B per GPU fixed).
 (one per GPU, backend nccl = RCCL); under an external launcher it checks WORLD_SIZE == N.  It never falls back to fewer
 ranks: fewer than N visible devices is an error.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with
+Prints ONE JSON line on rank 0.  A plain run (``bench.py --gpus N --steps K --warmup W``) does only what the headline needs:
+it sets up, brings the clocks up (``--prewarm-seconds``), runs W warm-up and K timed steps, writes ``--dump-outputs`` and prints
+the headline fields: metric, value, unit, higher_is_better, dtype, ms_per_step, ms_per_step_events (the same K timed steps
+measured with HIP events on the launch stream, beside the wall clock), config and roofline_step_hbm (arithmetic on
+ms_per_step).  The same holds for ``--model sins | combsubfast | combsubsuperfast``; the other ``--model`` workloads print
+their own lines.  ``--full`` runs everything else the benchmark measures or checks after the same timed steps, and its line
+adds
   roofline               the dominant kernel (the time-varying FIR, k_fir_blk6) INSIDE the step at the clocks' steady state: a
                          rocprofv3 --kernel-trace pass of this run (900 steps, the launches past the first third); frac = SURVEY 8-d
                          bytes of what one launch processes / that duration / 8 TB/s; bound "valu" (valu_frac beside it); frac_alone
@@ -23,11 +29,10 @@ Prints ONE JSON line on rank 0 (contract in the task statement), with
   also                   (N = 1) the other single-GPU BASELINE configs attested by the same command: the Sins cfg-3 step with its
                          dominant kernel's roofline, the as-shipped CombSubSuperFast model (informative), train_combsub = forward +
                          backward of the CombSub DSP behind a gradient gate against the oracle's adjoint, and the reference's loss
-  cfg4                   (the default N = 1 command, N = 8, or --cfg4) BASELINE cfg 4's per-GPU shape: 64 utterances per GPU,
+  cfg4                   (--full at N = 1 and N = 8, or --cfg4 in any run) BASELINE cfg 4's per-GPU shape: 64 utterances per GPU,
                          samples/s without and with the RCCL gather, interleaved rounds (a 1-rank communicator at N = 1)
-  parity_vs_oracle       the gate every line is printed behind: two utterances of the TIMED output against the oracle
+  parity_vs_oracle       the gate a --full line is printed behind: two utterances of the TIMED output against the oracle
                          (<= 1e-4 RMS abs, <= 1e-5 rel) -- a miss is SystemExit, not a field
-  ms_per_step_events     the same K timed steps measured with HIP events on the launch stream, beside the wall clock
   cpu_baseline           the numpy oracle (oracle/ddsp_oracle.py, a port of the reference algorithm) timed
                          on this host's cores over a bounded sample of the same workload (N=1 only); kind "reference" -- the
                          UNMODIFIED reference module itself, with the 1e-4 parity gate -- when a reference checkout
@@ -1334,8 +1339,41 @@ def bench_mel(a, rank, world, device):
     emit((res))
 
 
-def report_fast(a, rank, world, B, F, T, sizes, elapsed, gather_ms, f0, ctrls, noise, window, win):
-    """JSON line for CombSubFast / CombSubSuperFast: the dominant kernel is the fused
+def headline_line(a, world, B, F, T, sizes, win, elapsed, events_ms, gather_ms):
+    """The fields of the JSON line that the timed steps alone give: all a plain run prints, and what a ``--full`` line of the
+    same model starts from"""
+    ms = elapsed / a.steps * 1e3
+    alg_bytes = (8.0 + 4.0 * (sum(sizes) + 1) / HOP) * B * T          # out + noise + controls + f0 (SURVEY 8-d)
+    if a.model in FAST_MODELS:
+        metric = "audio samples/sec, %s 44.1kHz win%d hop512" % (
+            "CombSubSuperFast" if a.model == "combsubsuperfast" else "CombSubFast", win)
+        workload = ("%s B=%d/GPU x %.0f s utterances (F=%d, T=%d), %d x %d control bins, sr 44100, hop 512, "
+                    "DSP path (exciter phase + exciter + short-time spectral filter) from resident f0 / raw "
+                    "controls ~N(0,1) / noise" % (a.model, B, a.seconds, F, T, len(sizes), sizes[0]))
+    else:
+        metric = "audio samples/sec, %s 44.1kHz 256-harm hop512" % ("CombSub" if a.model == "combsub" else "Sins")
+        n = sizes[0]
+        workload = ("%s B=%d/GPU x %.0f s utterances (F=%d, T=%d), n_mag %d/%d/%d, sr 44100, hop 512, "
+                    "DSP path (HOT-1 + HOT-2) from resident f0 / raw controls ~N(0,1) / uniform noise, "
+                    "signal only" % (a.model, B, a.seconds, F, T, n, n, n))
+    res = {
+        "metric": metric, "value": B * world * T * a.steps / elapsed, "unit": "samples/s", "n_gpus": world, "steps": a.steps,
+        "warmup": a.warmup, "prewarm_s": a.prewarm_seconds, "ms_per_step": ms, "ms_per_step_events": events_ms,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": workload, "batch_per_gpu": B, "frames": F, "samples_per_utterance": T,
+                   "parallelism": "utterance-shard x%d" % world},
+        "roofline_step_hbm": {"bound": "hbm", "algorithmic_bytes_per_step": alg_bytes,
+                              "achieved": alg_bytes / (ms * 1e-3) / 1e9, "peak": 8000.0, "unit": "GB/s",
+                              "frac": alg_bytes / (ms * 1e-3) / 1e9 / 8000.0},
+    }
+    if gather_ms is not None:
+        res["gather_ms"] = gather_ms
+        res["gather_bytes_per_rank"] = 4.0 * B * T
+    return res
+
+
+def report_fast(a, rank, world, B, F, T, sizes, elapsed, events_ms, gather_ms, f0, ctrls, noise, window, win):
+    """``--full`` JSON line for CombSubFast / CombSubSuperFast: the dominant kernel is the fused
     short-time spectral filter k_stft_filter, timed alone with events on the launch stream."""
     from ddsp_svc_amd import synth
     exc = torch.randn(B, T, device=f0.device)
@@ -1357,26 +1395,15 @@ def report_fast(a, rank, world, B, F, T, sizes, elapsed, gather_ms, f0, ctrls, n
     k_ms = e0.elapsed_time(e1) / reps
     if rank != 0:
         return
-    sigma_c = sum(sizes)
     # the kernel reads exciter + noise + controls and writes the signal; the step regenerates the exciter from f0
-    k_bytes = (12.0 + 4.0 * sigma_c / HOP) * B * T
-    alg_bytes = (8.0 + 4.0 * (sigma_c + 1) / HOP) * B * T
+    k_bytes = (12.0 + 4.0 * sum(sizes) / HOP) * B * T
     kname = "k_stft_filter<%d>" % (4 if win == 2048 else 2)
     traffic = hbm_traffic("k_stft_filter") if (B, F) == (32, 862) and super_ else None
     pairs = (F + 2) // 2
     fft_flops = B * pairs * (3 * 5.0 * win * np.log2(win) + win * 30.0)
-    total = B * world * T * a.steps
-    value = total / elapsed
-    ms = elapsed / a.steps * 1e3
-    res = {
-        "metric": "audio samples/sec, %s 44.1kHz win%d hop512" % ("CombSubSuperFast" if super_ else "CombSubFast", win),
-        "value": value, "unit": "samples/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "prewarm_s": a.prewarm_seconds,
-        "ms_per_step": ms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32", "data": "synthetic",
-        "config": {"workload": "%s B=%d/GPU x %.0f s utterances (F=%d, T=%d), %d x %d control bins, sr 44100, hop 512, "
-                               "DSP path (exciter phase + exciter + short-time spectral filter) from resident f0 / raw "
-                               "controls ~N(0,1) / noise" % (a.model, B, a.seconds, F, T, len(sizes), sizes[0]),
-                   "batch_per_gpu": B, "frames": F, "samples_per_utterance": T, "parallelism": "utterance-shard x%d" % world},
+    res = headline_line(a, world, B, F, T, sizes, win, elapsed, events_ms, gather_ms)
+    value = res["value"]
+    res.update({
         "roofline": {"kernel": kname, "bound": "hbm", "achieved": k_bytes / (k_ms * 1e-3) / 1e9, "peak": 8000.0,
                      "unit": "GB/s", "frac": k_bytes / (k_ms * 1e-3) / 1e9 / 8000.0,
                      "traffic": traffic["bytes"] if traffic else None, "traffic_detail": traffic,
@@ -1384,12 +1411,7 @@ def report_fast(a, rank, world, B, F, T, sizes, elapsed, gather_ms, f0, ctrls, n
         "roofline_compute": {"kernel": kname, "bound": "valu", "unit": "TFLOP/s", "peak": 157.3,
                              "achieved": fft_flops / (k_ms * 1e-3) / 1e12, "frac": fft_flops / (k_ms * 1e-3) / 1e12 / 157.3,
                              "executed_flops_per_launch": fft_flops},
-        "roofline_step_hbm": {"bound": "hbm", "algorithmic_bytes_per_step": alg_bytes,
-                              "achieved": alg_bytes / (ms * 1e-3) / 1e9, "peak": 8000.0, "unit": "GB/s",
-                              "frac": alg_bytes / (ms * 1e-3) / 1e9 / 8000.0},
-    }
-    if gather_ms is not None:
-        res["gather_ms"] = gather_ms
+    })
     if world == 1 and not a.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline(a.model, F, sizes)
         res["cpu_baseline"]["gpu_over_cpu"] = value / res["cpu_baseline"]["value"]
@@ -1605,36 +1627,43 @@ def main(argv=None):
                     help="--model mel / cascade_ref: get_mel's key shift in semitones (the cascade's formant shift, main_diff.py:359)")
     ap.add_argument("--bins", type=int, default=256)
     ap.add_argument("--fir-impl", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baselines (of --full, and of --model mel)")
     ap.add_argument("--prewarm-seconds", type=float, default=0.5,
                     help="untimed clock ramp-up before the warm-up steps (0 disables)")
     ap.add_argument("--gather", action="store_true", help="also time the optional gather of the waveforms to rank 0")
     ap.add_argument("--only-steps", action="store_true",
                     help="run exactly warmup + steps of the step and nothing else (no clock ramp-up, no separately timed "
                          "kernels, no baselines): what tools/gpu_traffic.sh and the kernel-trace profiles wrap")
-    ap.add_argument("--no-module-mode", action="store_true", help="skip the control-mode (i) timing")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything else the benchmark measures or checks: the parity gate, "
+                         "the dominant kernel's roofline, the in-step trace and PMC passes, the other BASELINE configs "
+                         "(also, cfg4), module mode and the CPU baselines (a plain run prints the headline fields only)")
+    ap.add_argument("--no-module-mode", action="store_true", help="--full: skip the control-mode (i) timing")
     ap.add_argument("--no-live-traffic", action="store_true",
-                    help="do not run the rocprofv3 PMC passes; report the newest committed traffic summary instead")
-    ap.add_argument("--no-also", action="store_true", help="skip the Sins (cfg 3) / CombSubSuperFast lines of the N = 1 run")
+                    help="--full: do not run the rocprofv3 PMC passes; report the newest committed traffic summary instead")
+    ap.add_argument("--no-also", action="store_true", help="--full: skip the Sins (cfg 3) / CombSubSuperFast lines of the N = 1 run")
     ap.add_argument("--no-in-step-trace", action="store_true",
-                    help="do not run the kernel-trace pass that measures the dominant kernel inside the step (roofline.frac then uses the stand-alone time)")
+                    help="--full: do not run the kernel-trace pass that measures the dominant kernel inside the step (roofline.frac then uses the stand-alone time)")
     ap.add_argument("--trace-stats-out", default=None,
-                    help="write the per-kernel table of the in-step kernel-trace pass there (what profiles/*_kernel_stats.csv holds)")
+                    help="--full: write the per-kernel table of the in-step kernel-trace pass there (what profiles/*_kernel_stats.csv holds)")
     ap.add_argument("--cfg4", action="store_true",
-                    help="also run BASELINE cfg 4's per-GPU shape (64 utterances per GPU) -- default at --gpus 8")
+                    help="also run BASELINE cfg 4's per-GPU shape (64 utterances per GPU), with or without --full -- "
+                         "part of --full at --gpus 1 and 8")
     ap.add_argument("--cfg4-batch", type=int, default=64, help="utterances per GPU of the cfg-4 line (BASELINE: 64)")
     ap.add_argument("--cfg4-round-steps", type=int, default=10, help="steps per interleaved round of the cfg-4 line")
     ap.add_argument("--cfg4-keep-cache", action="store_true", help="(A/B) do not release the allocator's cached blocks before the cfg-4 line")
-    ap.add_argument("--no-cfg4", action="store_true", help="skip the cfg-4 line (part of the default N = 1 and N = 8 runs)")
+    ap.add_argument("--no-cfg4", action="store_true", help="skip the cfg-4 line (part of --full at N = 1 and N = 8)")
     ap.add_argument("--no-cfg4-gather", action="store_true", help="cfg-4 line without opening a 1-rank communicator at N = 1")
     ap.add_argument("--no-parity-gate", action="store_true",
-                    help="do not hold the timed output against the oracle before printing (A/B runs of broken ablation builds)")
+                    help="--full: do not hold the timed output against the oracle before printing (A/B runs of broken ablation builds)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned (rank 0's shard) as DIR/<name>.npy "
                          "(float32, at most 64 MB in all; a fixed seeded sample of rows beyond that)")
     a = ap.parse_args(argv)
     if a.dump_outputs and a.model not in ("combsub", "sins") + FAST_MODELS:
         ap.error("--dump-outputs: --model %s is not supported (combsub, sins, %s)" % (a.model, ", ".join(FAST_MODELS)))
+    if a.only_steps and a.full:
+        ap.error("--only-steps and --full exclude each other")
     if a.only_steps:
         a.prewarm_seconds = 0.0
 
@@ -1705,8 +1734,18 @@ def main(argv=None):
                               "ms_per_step": elapsed / a.steps * 1e3, "ms_per_step_events": events_ms}))
         return finish_ranks()
 
+    if not a.full:                                   # a plain run: the headline, and only what was asked for by name
+        cfg4 = cfg4_line(a, rank, world, device, F, n, comm) if a.cfg4 and a.model == "combsub" and not a.no_cfg4 else None
+        if rank == 0:
+            res = headline_line(a, world, B, F, T, sizes, win, elapsed, events_ms, gather_ms)
+            res.update(comm)
+            if cfg4 is not None:
+                res["cfg4"] = cfg4
+            emit(res)
+        return finish_ranks()
+
     if a.model in FAST_MODELS:
-        report_fast(a, rank, world, B, F, T, sizes, elapsed, gather_ms, f0, ctrls, noise, window, win)
+        report_fast(a, rank, world, B, F, T, sizes, elapsed, events_ms, gather_ms, f0, ctrls, noise, window, win)
         return finish_ranks()
 
     # ---- dominant kernel alone: the time-varying FIR (N = 2(n-1) taps), events on the launch stream.  Two forms ship:
@@ -1797,16 +1836,8 @@ def main(argv=None):
         else:
             per_launch, k_us, k_src = 1.0, fir_ms * 1e3, "alone (no in-step trace in this run): HIP events around 20 back-to-back launches"
         k_bytes, k_flops = filt_bytes * per_launch, fft_flops * per_launch
-        res = {
-            "metric": "audio samples/sec, CombSub 44.1kHz 256-harm hop512" if a.model == "combsub"
-                      else "audio samples/sec, Sins 44.1kHz 256-harm hop512",
-            "value": value, "unit": "samples/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "prewarm_s": a.prewarm_seconds,
-            "ms_per_step": ms, "ms_per_step_events": events_ms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "%s B=%d/GPU x %.0f s utterances (F=%d, T=%d), n_mag %d/%d/%d, sr 44100, hop 512, "
-                                   "DSP path (HOT-1 + HOT-2) from resident f0 / raw controls ~N(0,1) / uniform noise, "
-                                   "signal only" % (a.model, B, a.seconds, F, T, n, n, n),
-                       "batch_per_gpu": B, "frames": F, "samples_per_utterance": T, "parallelism": "utterance-shard x%d" % world},
+        res = headline_line(a, world, B, F, T, sizes, win, elapsed, events_ms, gather_ms)
+        res.update({
             "roofline": {"kernel": kname.rstrip("<"), "bound": "valu",
                          "achieved": k_bytes / (k_us * 1e-6) / 1e9, "peak": 8000.0, "unit": "GB/s",
                          "frac": k_bytes / (k_us * 1e-6) / 1e9 / 8000.0,
@@ -1846,10 +1877,7 @@ def main(argv=None):
                                           "avg_ms": mfma_ms, "algorithmic_flops_per_launch": fir_flops,
                                           "note": "the direct form on v_mfma_f32_16x16x4_f32, used for shapes outside the "
                                                   "FFT form; ~2.05 GHz under load, 1.29x issued/algorithmic MFMAs"},
-            "roofline_step_hbm": {"bound": "hbm", "algorithmic_bytes_per_step": alg_bytes,
-                                  "achieved": alg_bytes / (ms * 1e-3) / 1e9, "peak": 8000.0, "unit": "GB/s",
-                                  "frac": alg_bytes / (ms * 1e-3) / 1e9 / 8000.0},
-        }
+        })
         res.update(comm)
         res["parity_vs_oracle"] = parity
         res["roofline_step_traffic"] = None if tr is None else {
@@ -1860,9 +1888,6 @@ def main(argv=None):
             res["cfg4"] = cfg4
         if world == 1 and a.model == "combsub" and not a.no_also:
             res["also"] = also_lines(a, device, B, F, n, want_live)
-        if gather_ms is not None:
-            res["gather_ms"] = gather_ms
-            res["gather_bytes_per_rank"] = 4.0 * B * T
         if world == 1 and not a.no_module_mode:
             res["value_module_mode"] = module_mode(a.model, B, F, n, device, max(5, a.steps // 5), 3)
             # DSP-only step with the uniform noise drawn inside the noise filter (opt-in; algorithmic bytes 10.01 / sample)

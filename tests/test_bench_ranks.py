@@ -222,3 +222,47 @@ def test_parity_gate_refuses_a_wrong_output():
     assert status == "ok", rec
     assert rec["rows"] == [0, 2] and rec["rms_abs"] <= 1e-4 and rec["rms_rel"] <= 1e-5
     assert refused
+
+
+def _plain_worker(dump_dir, q):
+    os.environ.update({"RANK": "0", "WORLD_SIZE": "1", "LOCAL_RANK": "0"})
+    try:
+        bench = _install_emulator()
+
+        def not_in_a_plain_run(*args, **kwargs):
+            raise AssertionError("a plain run reached a leg of --full")
+        for name in ("cfg4_line", "parity_gate", "live_traffic", "in_step_kernel_times", "also_lines", "module_mode", "cpu_baseline",
+                     "cpu_baseline_aten_chain", "aten_chain_on_gpu", "report_fast"):
+            setattr(bench, name, not_in_a_plain_run)
+        argv = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--batch-per-gpu", "2", "--seconds", "0.03", "--bins", "65",
+                "--prewarm-seconds", "0", "--dump-outputs", dump_dir]
+        buf = io.StringIO()
+        with redirect_stdout(buf):
+            bench.main(argv)
+            bench.flush_emit()
+        q.put(("ok", [ln for ln in buf.getvalue().splitlines() if ln.startswith("{")]))
+    except BaseException as e:
+        import traceback
+        q.put(("error", "%s: %s\n%s" % (type(e).__name__, e, traceback.format_exc())))
+
+
+def test_plain_run_is_the_headline_alone(tmp_path):
+    """without --full the run times its steps, writes --dump-outputs and prints the headline fields, and reaches none of the
+    legs that --full adds (each is replaced by one that raises)"""
+    import numpy as np
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    p = ctx.Process(target=_plain_worker, args=(str(tmp_path), q))
+    p.start()
+    status, payload = q.get(timeout=300)
+    p.join(timeout=60)
+    assert status == "ok", payload
+    assert len(payload) == 1, payload
+    line = json.loads(payload[0])
+    T = (int(0.03 * 44100) // 512 + 1) * 512
+    assert line["metric"] == "audio samples/sec, CombSub 44.1kHz 256-harm hop512" and line["unit"] == "samples/s"
+    assert line["higher_is_better"] is True and line["dtype"] == "f32" and line["steps"] == 2 and line["warmup"] == 1
+    assert line["ms_per_step"] > 0 and abs(line["value"] - 2 * T / (line["ms_per_step"] * 1e-3)) <= 1e-6 * line["value"]
+    for k in ("roofline", "parity_vs_oracle", "also", "cfg4", "cpu_baseline", "value_module_mode", "in_kernel_noise"):
+        assert k not in line, k
+    assert np.load(tmp_path / "signal.npy").shape == (2, T)

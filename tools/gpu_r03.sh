@@ -10,14 +10,14 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
   timeout 900 python -m pytest tests -m gpu -x -q 2>&1 | grep -E "passed|failed|error" | tail -3 | tee "$O/${V}_pytest_gpu.log"
   timeout 200 python __graft_entry__.py --smoke 2>&1 | tail -4 | tee "$O/${V}_smoke.log"
 fi
-( time timeout 400 python bench.py ) 2>&1 | tail -5 > "$O/${V}_bench_combsub.log"; grep '^{' "$O/${V}_bench_combsub.log" | tail -1 > "$O/${V}_bench_combsub.json"
-timeout 300 python bench.py --model sins --no-also 2>&1 | tail -1 > "$O/${V}_bench_sins.json"
+( time timeout 400 python bench.py --full ) 2>&1 | tail -5 > "$O/${V}_bench_combsub.log"; grep '^{' "$O/${V}_bench_combsub.log" | tail -1 > "$O/${V}_bench_combsub.json"
+timeout 300 python bench.py --full --model sins --no-also 2>&1 | tail -1 > "$O/${V}_bench_sins.json"
 timeout 200 python bench.py --cfg4 --no-cpu-baseline --no-module-mode --no-live-traffic --no-also --steps 30 2>&1 | tail -1 > "$O/${V}_bench_cfg4_1rank.json"
 timeout 100 python bench.py --gpus 2 --no-cpu-baseline > "$O/${V}_bench_gpus2_on_1gpu.log" 2>&1; echo "exit $?" >> "$O/${V}_bench_gpus2_on_1gpu.log"
 timeout 300 python bench.py --model cascade_seam --batch-per-gpu 64 2>&1 | tail -1 > "$O/${V}_bench_cascade_seam.json"
-DDSP_HIP_ONE_STREAM=1 timeout 200 python bench.py --no-cpu-baseline --no-module-mode --no-live-traffic --no-also 2>&1 | tail -1 > "$O/${V}_bench_combsub_one_stream.json"
+DDSP_HIP_ONE_STREAM=1 timeout 200 python bench.py --full --no-cpu-baseline --no-module-mode --no-live-traffic --no-also 2>&1 | tail -1 > "$O/${V}_bench_combsub_one_stream.json"
 for m in combsubfast combsubsuperfast mel sinesrc rssloss; do
-  timeout 200 python bench.py --model $m --no-cpu-baseline 2>&1 | tail -1 > "$O/${V}_bench_$m.json"
+  timeout 200 python bench.py --full --model $m --no-cpu-baseline 2>&1 | tail -1 > "$O/${V}_bench_$m.json"
 done
 cd /tmp
 for m in combsub sins combsubsuperfast; do

@@ -17,7 +17,7 @@ set -u
 R=${GRAFT_REPO_ROOT:-$(pwd)}; cd "$R"; O="$R/gpurun_out"; mkdir -p "$O"; export TMPDIR=/tmp
 export V=${V:-r04}
 MODEL=${MODEL:-combsub}
-BENCH="python bench.py --model $MODEL --no-cpu-baseline --no-module-mode --no-live-traffic --no-also"
+BENCH="python bench.py --full --model $MODEL --no-cpu-baseline --no-module-mode --no-live-traffic --no-also"
 FIR_TESTS="tests/test_parity.py tests/test_fullsize_gpu.py tests/test_noise_rng.py tests/test_baseline_shapes.py tests/test_fuzz.py"
 
 summary() {
@@ -130,9 +130,9 @@ refresh)
   # training steps, the streaming-shape latencies, cfg 4's per-GPU shape on a 1-rank communicator
   timeout 1500 python -m pytest tests -m gpu -x -q 2>&1 | grep -E "passed|failed|error" | tail -3 | tee "$O/${V}_pytest_gpu.log"
   timeout 300 python __graft_entry__.py --smoke 2>&1 | grep -v Warning | tail -4 | tee "$O/${V}_smoke.log"
-  ( time timeout 600 python bench.py ) 2>"$O/${V}_bench_combsub.err" | tail -1 > "$O/${V}_bench_combsub.json"; tail -4 "$O/${V}_bench_combsub.err"
+  ( time timeout 600 python bench.py --full ) 2>"$O/${V}_bench_combsub.err" | tail -1 > "$O/${V}_bench_combsub.json"; tail -4 "$O/${V}_bench_combsub.err"
   for m in sins combsubsuperfast combsubfast rssloss mel sinesrc; do
-    timeout 300 python bench.py --model $m --no-also --no-cpu-baseline --no-live-traffic 2>/dev/null | tail -1 > "$O/${V}_bench_$m.json"
+    timeout 300 python bench.py --full --model $m --no-also --no-cpu-baseline --no-live-traffic 2>/dev/null | tail -1 > "$O/${V}_bench_$m.json"
   done
   timeout 300 python bench.py --cfg4 --no-also --no-cpu-baseline --no-live-traffic --no-module-mode 2>/dev/null | tail -1 > "$O/${V}_bench_cfg4_1rank.json"
   summary
@@ -160,7 +160,7 @@ reference)
   # reference's OWN classes, on the MI355X; then the bench line with cpu_baseline.kind = "reference" and the parity gate
   echo "DDSP_REFERENCE_PATH=$DDSP_REFERENCE_PATH"; ls "$DDSP_REFERENCE_PATH" | head -3
   timeout 1200 python -m pytest tests/test_modules.py tests/test_backward_fir.py tests/test_backward_fast.py tests/test_mel.py tests/test_sine_source.py tests/test_cascade_seam.py tests/test_loss.py -m gpu -q -rA -s 2>&1 | grep -v "^\s*$" | grep -E "passed|failed|PASSED|FAILED|SKIPPED|rms error|training step|Error|error" | tee "$O/${V}_reference_on_gpu.log" | tail -60
-  timeout 900 python bench.py --no-module-mode --no-live-traffic --no-also 2>"$O/${V}_bench_reference.err" | tail -1 > "$O/${V}_bench_reference.json"
+  timeout 900 python bench.py --full --no-module-mode --no-live-traffic --no-also 2>"$O/${V}_bench_reference.err" | tail -1 > "$O/${V}_bench_reference.json"
   timeout 900 python bench.py --model cascade_ref --batch-per-gpu 64 2>"$O/${V}_bench_cascade_ref.err" | tail -1 > "$O/${V}_bench_cascade_ref.json"
   cat "$O/${V}_bench_cascade_ref.json" | cut -c1-1500; tail -3 "$O/${V}_bench_cascade_ref.err"
   python - <<'PY'
@@ -175,13 +175,13 @@ tests)
   timeout 600 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -8 | tee "$O/${V}_smoke.log"
   ;;
 bench)
-  timeout 900 python bench.py 2>&1 | tail -1 > "$O/${V}_bench_default.json"
+  timeout 900 python bench.py --full 2>&1 | tail -1 > "$O/${V}_bench_default.json"
   V=$V summary
   trace default X=1
   ;;
 model)
   MODEL=$2
-  timeout 600 python bench.py --model $MODEL --no-cpu-baseline --no-module-mode --no-live-traffic --no-also 2>&1 | tail -1 > "$O/${V}_bench_$MODEL.json"
+  timeout 600 python bench.py --full --model $MODEL --no-cpu-baseline --no-module-mode --no-live-traffic --no-also 2>&1 | tail -1 > "$O/${V}_bench_$MODEL.json"
   summary
   trace $MODEL X=1
   ;;

@@ -11,7 +11,7 @@ set -u
 R=${GRAFT_REPO_ROOT:-$(pwd)}; cd "$R"; O="$R/gpurun_out"; mkdir -p "$O"; export TMPDIR=/tmp
 export V=${V:-r05}
 MODEL=${MODEL:-combsub}
-BENCH="python bench.py --model $MODEL --no-cpu-baseline --no-module-mode --no-live-traffic --no-also --no-cfg4"
+BENCH="python bench.py --full --model $MODEL --no-cpu-baseline --no-module-mode --no-live-traffic --no-also --no-cfg4"
 
 line() {  # line <file>: ms_per_step, events, kernel
 python - "$1" <<'PY'
@@ -71,7 +71,7 @@ lanes)
   echo "== timeline, lanes"; gaps lanes X=1 | head -80
   echo "== timeline, unsplit"; gaps unsplit DDSP_HIP_LANE_ROWS=1 | head -50
   echo "== the driver's command"
-  ( time timeout 900 python bench.py ) 2>"$O/${V}_bench_default.err" | tail -1 > "$O/${V}_bench_default.json"; tail -4 "$O/${V}_bench_default.err"
+  ( time timeout 900 python bench.py --full ) 2>"$O/${V}_bench_default.err" | tail -1 > "$O/${V}_bench_default.json"; tail -4 "$O/${V}_bench_default.err"
   python - <<'PY'
 import json, os
 V = os.environ["V"]
@@ -218,7 +218,7 @@ bwdpmc)
   ;;
 sweep) sweep ;;
 default)
-  ( time timeout 900 python bench.py ) 2>"$O/${V}_bench_default.err" | tail -1 > "$O/${V}_bench_default.json"; tail -4 "$O/${V}_bench_default.err"
+  ( time timeout 900 python bench.py --full ) 2>"$O/${V}_bench_default.err" | tail -1 > "$O/${V}_bench_default.json"; tail -4 "$O/${V}_bench_default.err"
   line "$O/${V}_bench_default.json"
   ;;
 *) echo "unknown mode $mode"; exit 2;;

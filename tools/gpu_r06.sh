@@ -11,7 +11,7 @@ set -u
 R=${GRAFT_REPO_ROOT:-$(pwd)}; cd "$R"; O="$R/gpurun_out"; mkdir -p "$O"; export TMPDIR=/tmp
 export V=${V:-r06}
 MODEL=${MODEL:-combsub}
-BENCH="python bench.py --model $MODEL --no-cpu-baseline --no-module-mode --no-live-traffic --no-also --no-cfg4"
+BENCH="python bench.py --full --model $MODEL --no-cpu-baseline --no-module-mode --no-live-traffic --no-also --no-cfg4"
 
 line() {  # line <file>: ms_per_step, events, kernel
 python - "$1" <<'PY'
@@ -86,10 +86,10 @@ final)
   # streaming-shape latencies, the step + mel pair, the communicator check, cfg 5 with the reference's networks
   timeout 2400 python -m pytest tests -m gpu -q -rs 2>&1 | grep -E "passed|failed|error|SKIPPED" | tee "$O/${V}_pytest_gpu.log"
   timeout 600 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | grep smoke | tee "$O/${V}_smoke.log"
-  ( time timeout 1200 python bench.py --trace-stats-out "$O/${V}_bench_in_step_kernel_stats.csv" ) 2>"$O/${V}_bench_combsub.err" | tail -1 > "$O/${V}_bench_combsub.json"; tail -4 "$O/${V}_bench_combsub.err"
+  ( time timeout 1200 python bench.py --full --trace-stats-out "$O/${V}_bench_in_step_kernel_stats.csv" ) 2>"$O/${V}_bench_combsub.err" | tail -1 > "$O/${V}_bench_combsub.json"; tail -4 "$O/${V}_bench_combsub.err"
   line "$O/${V}_bench_combsub.json"
   for m in sins combsubsuperfast combsubfast rssloss mel sinesrc; do
-    timeout 300 python bench.py --model $m --no-also --no-cpu-baseline --no-live-traffic 2>/dev/null | tail -1 > "$O/${V}_bench_$m.json"
+    timeout 300 python bench.py --full --model $m --no-also --no-cpu-baseline --no-live-traffic 2>/dev/null | tail -1 > "$O/${V}_bench_$m.json"
   done
   echo "== B sweep"; for B in 16 32 64 128 256; do f="$O/${V}_sweep_B${B}.json"; timeout 300 $BENCH --batch-per-gpu $B --steps 60 2>&1 | tail -1 > "$f"; line "$f"; done
   export LAST=150
@@ -136,7 +136,7 @@ for m in ("sins", "combsubsuperfast", "combsubfast", "rssloss", "mel", "sinesrc"
 PY
   ;;
 default)
-  ( time timeout 900 python bench.py ) 2>"$O/${V}_bench_default.err" | tail -1 > "$O/${V}_bench_default.json"; tail -4 "$O/${V}_bench_default.err"
+  ( time timeout 900 python bench.py --full ) 2>"$O/${V}_bench_default.err" | tail -1 > "$O/${V}_bench_default.json"; tail -4 "$O/${V}_bench_default.err"
   line "$O/${V}_bench_default.json"
   ;;
 *) echo "unknown mode $mode"; exit 2;;
