@@ -94,6 +94,9 @@ SIGNATURES = {
     "ddsp_hip_mel_shifted_frames": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "ddsp_hip_mel_shifted_spectrogram": (c_int, [P, c_int, c_int, P, c_int, c_int, c_int, c_int, c_int, c_float, P, P, c_int,
                                                  c_float, P, c_long, c_long, c_long, P]),
+    "ddsp_hip_splice_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "ddsp_hip_sola_splice": (c_int, [P, c_long, c_int, c_long, c_int, c_int, c_int, c_int, P, P, P, P, c_int, P, P, P, c_size_t, P]),
+    "ddsp_hip_phase_vocoder": (c_int, [P, P, P, P, c_int, P, P, c_size_t, P]),
 }
 
 MODE_ROLL, MODE_HANN, MODE_DYNAMIC = 0, 1, 2

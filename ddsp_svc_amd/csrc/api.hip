@@ -3,6 +3,7 @@
 #include "../../include/ddsp_hip.h"
 #include "kernels.h"
 #include "philox.h"
+#include "splice.h"
 #include <atomic>
 #include <stdio.h>
 #include <mutex>
@@ -1319,6 +1320,38 @@ int ddsp_hip_stft_loss_backward(const float* spec_true, const float* spec_pred, 
   if (launch_sss_wave_bwd(spec_true, spec_pred, B, T, n_fft, hop, frames, tables, norms, inv_window_norm, eps, alpha, grad_out,
                           wrt_true ? 1 : 0, d_x, ld_dx, accumulate ? 1 : 0, (float*)ws, S(stream)) != 0)
     return DDSP_HIP_ESHAPE;
+  return finish();
+}
+
+size_t ddsp_hip_splice_workspace_bytes(int B, int C, int use_pv) {
+  if (B < 1 || C < 1 || C > 16384) return 0;
+  return splice_ws_bytes(B, C, use_pv ? 1 : 0);
+}
+
+int ddsp_hip_sola_splice(const float* audio, long ld, int B, long L, int Bf, int C, int search, int D, const float* buf_in,
+                         float* buf_out, const float* fade_in, const float* fade_out, int use_pv, float* out, long long* shift,
+                         void* ws, size_t ws_bytes, void* stream) {
+  if (B < 0 || Bf < 1 || D < 1) return DDSP_HIP_EINVAL;
+  if (C < 1 || C > 16384 || search < 0 || search > 4096 || Bf > (1 << 30) || B > 65535) return DDSP_HIP_ESHAPE;
+  if (L < (long)Bf + C + search + D || ld < L) return DDSP_HIP_EINVAL;
+  if (B == 0) return 0;
+  if (!audio || !buf_in || !buf_out || !fade_in || !fade_out || !out || !shift) return DDSP_HIP_EINVAL;
+  if (buf_in == buf_out) return DDSP_HIP_EINVAL;                // the finishing kernel's workgroups read one while they write the other
+  if (!ws || ws_bytes < splice_ws_bytes(B, C, use_pv ? 1 : 0)) return DDSP_HIP_EWS;
+  if (reinterpret_cast<uintptr_t>(ws) & 15) return DDSP_HIP_EINVAL;
+  launch_sola_splice(audio, ld, B, L - ((long)Bf + C + search + D), Bf, C, search, buf_in, buf_out, fade_in, fade_out, use_pv ? 1 : 0, out,
+                     shift, ws, S(stream));
+  return finish();
+}
+
+int ddsp_hip_phase_vocoder(const float* a, const float* b, const float* fade_out, const float* fade_in, int n, float* out,
+                           void* ws, size_t ws_bytes, void* stream) {
+  if (n < 1) return DDSP_HIP_EINVAL;
+  if (n > 16384) return DDSP_HIP_ESHAPE;
+  if (!a || !b || !fade_out || !fade_in || !out) return DDSP_HIP_EINVAL;
+  if (!ws || ws_bytes < splice_ws_bytes(1, n, 1)) return DDSP_HIP_EWS;
+  if (reinterpret_cast<uintptr_t>(ws) & 15) return DDSP_HIP_EINVAL;
+  launch_phase_vocoder(a, b, fade_out, fade_in, n, out, ws, S(stream));
   return finish();
 }
 

@@ -176,4 +176,12 @@ size_t sss_wave_bwd_ws_bytes(int B, int n, int hop, int frames);
 int launch_sss_wave_bwd(const float* spec_t, const float* spec_p, int B, int T, int n, int hop, int frames, const float* tab,
                         const float* norms, float inv_wn, float eps, float alpha, const float* grad_out, int wrt_true,
                         float* dx, long ld_dx, int accumulate, float* ws, hipStream_t st);
+// the real-time caller's block splice (splice.h, compiled into api.hip): SOLA search + crossfade in 2 launches, with the phase
+// vocoder 3; the shift stays on the device.  shift: [B] int64.  ws: splice_ws_bytes(B, C, use_pv), 16-byte aligned
+size_t splice_ws_bytes(int B, int C, int use_pv);
+void launch_sola_splice(const float* audio, long ld, int B, long off, int Bf, int C, int S, const float* buf_in, float* buf_out,
+                        const float* fade_in, const float* fade_out, int use_pv, float* out, long long* shift, void* ws,
+                        hipStream_t st);
+void launch_phase_vocoder(const float* a, const float* b, const float* fade_out, const float* fade_in, int n, float* out, void* ws,
+                          hipStream_t st);
 }  // namespace ddsp

@@ -427,6 +427,28 @@ int ddsp_hip_stft_loss_backward(const float* spec_true, const float* spec_pred, 
                                 const float* grad_out, int wrt_true, float* d_x, long ld_dx, int accumulate, void* ws,
                                 size_t ws_bytes, void* stream);
 
+/* The real-time caller's splice of consecutive output blocks (gui.py:431-456).  These three entry points came after version 165
+ * without a version step: a caller that must run against older builds looks them up by name (dlsym) before use.
+ * Per utterance b of B:
+ * seg = audio[b, L - (Bf + C + S + D) : L - D]; shift = the first argmax over s = 0 .. S of
+ * sum_j seg[s + j] buf_in[b, j] / sqrt(sum_j seg[s + j]^2 + 1e-8) (j < C, float64 sums); tmp = seg[shift : shift + Bf + C];
+ * tmp[:C] = tmp[:C] * fade_in + buf_in[b] * fade_out (two float32 roundings, the torch chain's), or with use_pv
+ * phase_vocoder(buf_in[b], tmp[:C], fade_out, fade_in) (gui.py:15-32: float64 sums of float32 twiddles and cosines, the phase
+ * arguments reduced exactly in integers);
+ * out[b] = tmp[:Bf], buf_out[b] = tmp[Bf:] (after the crossfade: with Bf < C it holds crossfaded samples), shift[b] (int64).
+ * audio row stride ld >= L >= Bf + C + S + D; Bf >= 1, D >= 1 (DDSP_HIP_EINVAL); 1 <= C <= 16384, 0 <= S <= 4096
+ * (DDSP_HIP_ESHAPE otherwise).  buf_in and buf_out are distinct [B, C] buffers: a session ping-pongs them.  2 launches, 3 with
+ * use_pv; no synchronisation (the shift never reaches the host).  ws: ddsp_hip_splice_workspace_bytes(B, C, use_pv) bytes,
+ * 16-byte aligned. */
+size_t ddsp_hip_splice_workspace_bytes(int B, int C, int use_pv);
+int ddsp_hip_sola_splice(const float* audio, long ld, int B, long L, int Bf, int C, int S, int D, const float* buf_in,
+                         float* buf_out, const float* fade_in, const float* fade_out, int use_pv, float* out, long long* shift,
+                         void* ws, size_t ws_bytes, void* stream);
+/* gui.py:15-32 on its own: out[n] = phase_vocoder(a, b, fade_out, fade_in), 1 <= n <= 16384 (2 launches; out may be b).
+ * ws: ddsp_hip_splice_workspace_bytes(1, n, 1) bytes, 16-byte aligned. */
+int ddsp_hip_phase_vocoder(const float* a, const float* b, const float* fade_out, const float* fade_in, int n, float* out,
+                           void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
