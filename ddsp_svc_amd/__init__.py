@@ -8,9 +8,10 @@ Sins/CombSub forward pass of yxlllc/DDSP-SVC).
   nsf_source -- nsf_hifigan.models.SourceModuleHnNSF (SineGen + merge), the vocoder's harmonic source
   loss      -- ddsp/loss.py SSSLoss / RSSLoss (the STFT of any size below 2049 as an in-kernel chirp-z transform, the loss and
                its gradient in the same kernels; torch.stft only above that)
+  resample  -- torchaudio's sinc resampling (functional.resample / transforms.Resample) as an f32 MFMA GEMM
   splice    -- the real-time caller's block splice (gui.py:431-456): SOLA search, crossfade, phase vocoder
   sharding  -- utterance sharding across the GPUs of a node (+ optional RCCL gather)
 """
-from . import _ffi, build, core, loss, mel, nsf_source, splice, synth  # noqa: F401
+from . import _ffi, build, core, loss, mel, nsf_source, resample, splice, synth  # noqa: F401
 
 __version__ = "0.1.0"

@@ -97,6 +97,9 @@ SIGNATURES = {
     "ddsp_hip_splice_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "ddsp_hip_sola_splice": (c_int, [P, c_long, c_int, c_long, c_int, c_int, c_int, c_int, P, P, P, P, c_int, P, P, P, c_size_t, P]),
     "ddsp_hip_phase_vocoder": (c_int, [P, P, P, P, c_int, P, P, c_size_t, P]),
+    "ddsp_hip_resample_table_bytes": (c_size_t, [P, c_int, c_int, c_int]),
+    "ddsp_hip_resample_table": (c_int, [P, c_int, c_int, c_int, P, c_size_t]),
+    "ddsp_hip_resample": (c_int, [P, c_long, c_long, c_int, c_long, P, c_long, P, c_size_t, c_int, c_int, c_int, P]),
 }
 
 MODE_ROLL, MODE_HANN, MODE_DYNAMIC = 0, 1, 2

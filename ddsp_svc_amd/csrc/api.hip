@@ -4,6 +4,7 @@
 #include "kernels.h"
 #include "philox.h"
 #include "splice.h"
+#include "resample.h"
 #include <atomic>
 #include <stdio.h>
 #include <mutex>
@@ -1352,6 +1353,31 @@ int ddsp_hip_phase_vocoder(const float* a, const float* b, const float* fade_out
   if (!ws || ws_bytes < splice_ws_bytes(1, n, 1)) return DDSP_HIP_EWS;
   if (reinterpret_cast<uintptr_t>(ws) & 15) return DDSP_HIP_EINVAL;
   launch_phase_vocoder(a, b, fade_out, fade_in, n, out, ws, S(stream));
+  return finish();
+}
+
+size_t ddsp_hip_resample_table_bytes(const float* bank, int orig, int new_, int K) { return resample_table_bytes(bank, orig, new_, K); }
+
+int ddsp_hip_resample_table(const float* bank, int orig, int new_, int K, void* table, size_t table_bytes) {
+  if (!bank || !table) return DDSP_HIP_EINVAL;
+  if (!resample_rates_ok(orig, new_, K)) return DDSP_HIP_ESHAPE;
+  const size_t need = resample_table_bytes(bank, orig, new_, K);
+  if (need == 0) return DDSP_HIP_ESHAPE;
+  if (table_bytes < need) return DDSP_HIP_EWS;
+  return resample_table(bank, orig, new_, K, table, table_bytes) ? 0 : DDSP_HIP_ESHAPE;
+}
+
+int ddsp_hip_resample(const float* x, long ldx, long sx, int B, long L, float* y, long ldy, const void* table,
+                      size_t table_bytes, int orig, int new_, int width, void* stream) {
+  if (B < 1 || L < 0 || width < 1 || sx < 0 || ldx < 0 || ldy < 0) return DDSP_HIP_EINVAL;   // stride 0: an expanded tensor
+  if (!resample_rates_ok(orig, new_, 2 * width + orig) || L > (1L << 40)) return DDSP_HIP_ESHAPE;
+  const long T = ((long)new_ * L + orig - 1) / orig;
+  if (B > 1 && ldy < T) return DDSP_HIP_EINVAL;       // output rows must not overlap
+  if (T == 0) return 0;
+  if (!x || !y || !table) return DDSP_HIP_EINVAL;
+  if (table_bytes < resample::tap_section(resample::tiles_of(new_))) return DDSP_HIP_EWS;
+  if (reinterpret_cast<uintptr_t>(table) & 15) return DDSP_HIP_EINVAL;
+  launch_resample(x, ldx, sx, B, L, y, ldy, table, orig, new_, width, S(stream));
   return finish();
 }
 

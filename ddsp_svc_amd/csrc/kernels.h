@@ -184,4 +184,11 @@ void launch_sola_splice(const float* audio, long ld, int B, long off, int Bf, in
                         hipStream_t st);
 void launch_phase_vocoder(const float* a, const float* b, const float* fade_out, const float* fade_in, int n, float* out, void* ws,
                           hipStream_t st);
+// band-limited resampling (resample.h, compiled into api.hip): torchaudio's sinc resample as an f32 MFMA GEMM.  The table is
+// built on the host from the float32 [n, K] bank (reduced rates o = orig / gcd, n = new / gcd, K = 2 width + o)
+bool resample_rates_ok(int o, int n, int K);
+size_t resample_table_bytes(const float* bank, int o, int n, int K);
+bool resample_table(const float* bank, int o, int n, int K, void* out, size_t bytes);
+void launch_resample(const float* x, long ldx, long sx, int B, long L, float* y, long ldy, const void* table, int o, int n,
+                     int w, hipStream_t st);
 }  // namespace ddsp

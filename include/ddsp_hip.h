@@ -449,6 +449,28 @@ int ddsp_hip_sola_splice(const float* audio, long ld, int B, long L, int Bf, int
 int ddsp_hip_phase_vocoder(const float* a, const float* b, const float* fade_out, const float* fade_in, int n, float* out,
                            void* ws, size_t ws_bytes, void* stream);
 
+/* Band-limited resampling, torchaudio's sinc resample (torchaudio.functional.resample / transforms.Resample: F.pad(x, (w, w + o))
+ * then conv1d with the [n, 1, K] bank at stride o, the blocks interleaved and cut to T = ceil(n L / o)).  These three entry points
+ * came after version 165 without a version step: a caller that must run against older builds looks them up by name (dlsym)
+ * before use.  orig / new_ are the REDUCED rates o = orig_freq / gcd, n = new_freq / gcd (1 .. 4096), K = 2 width + o.
+ * ddsp_hip_resample_table_bytes: host bank [n, K] float32 (host memory) -> the bytes of its table; 0 when the rates are out of
+ * range or a tile of 32 phases has a live band (taps that are not exactly 0.0f) wider than 65 536 taps.
+ * ddsp_hip_resample_table: writes that table into HOST memory (the caller copies it to the device once and keeps it);
+ * DDSP_HIP_ESHAPE out of range, DDSP_HIP_EWS short.  Only the band of live taps is kept: the result differs from the full
+ * convolution by the order of the sums alone (for finite input).
+ * ddsp_hip_resample: y[b ldy + t] = sum_k xpad_b[q o + k] bank[j, k], t = q n + j < T, xpad_b[p] = x[b ldx + (p - width) sx]
+ * inside [0, L) and 0 outside, for b < B.  B >= 1, L >= 0 (T = 0: nothing is launched), sx >= 0 and ldx >= 0 (0: an expanded
+ * input, every element read from the same address), ldy >= T when B > 1
+ * (DDSP_HIP_EINVAL otherwise); table: the device copy, 16-byte aligned.  f32 MFMA, one launch per 65 535 utterances; no
+ * allocation, no synchronisation.  table must be the device copy of what ddsp_hip_resample_table wrote for the same orig,
+ * new_ and K = 2 width + orig, whole (table_bytes as ddsp_hip_resample_table_bytes gave it): the host cannot read the device
+ * copy, so only its header size is checked here.  The kernel compares the table's header with (orig, new_, K) and, when they
+ * differ, reads no tap and writes NaN to every output instead. */
+size_t ddsp_hip_resample_table_bytes(const float* bank, int orig, int new_, int K);
+int ddsp_hip_resample_table(const float* bank, int orig, int new_, int K, void* table, size_t table_bytes);
+int ddsp_hip_resample(const float* x, long ldx, long sx, int B, long L, float* y, long ldy, const void* table,
+                      size_t table_bytes, int orig, int new_, int width, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
