@@ -10,8 +10,9 @@ Sins/CombSub forward pass of yxlllc/DDSP-SVC).
                its gradient in the same kernels; torch.stft only above that)
   resample  -- torchaudio's sinc resampling (functional.resample / transforms.Resample) as an f32 MFMA GEMM
   splice    -- the real-time caller's block splice (gui.py:431-456): SOLA search, crossfade, phase vocoder
+  features  -- the frame features of the real-time path: volume, silence mask / gate, salience decode, F0 track
   sharding  -- utterance sharding across the GPUs of a node (+ optional RCCL gather)
 """
-from . import _ffi, build, core, loss, mel, nsf_source, resample, splice, synth  # noqa: F401
+from . import _ffi, build, core, features, loss, mel, nsf_source, resample, splice, synth  # noqa: F401
 
 __version__ = "0.1.0"

@@ -100,6 +100,13 @@ SIGNATURES = {
     "ddsp_hip_resample_table_bytes": (c_size_t, [P, c_int, c_int, c_int]),
     "ddsp_hip_resample_table": (c_int, [P, c_int, c_int, c_int, P, c_size_t]),
     "ddsp_hip_resample": (c_int, [P, c_long, c_long, c_int, c_long, P, c_long, P, c_size_t, c_int, c_int, c_int, P]),
+    "ddsp_hip_volume": (c_int, [P, c_long, c_int, c_long, c_int, P, P]),
+    "ddsp_hip_gate": (c_int, [P, c_long, P, c_int, c_long, c_int, c_float, c_int, P, c_long, P]),
+    "ddsp_hip_decode_salience": (c_int, [P, c_long, P, c_float, P, P]),
+    "ddsp_hip_f0_track_workspace_bytes": (c_size_t, [c_int, c_long, c_long]),
+    "ddsp_hip_f0_track": (c_int, [P, c_long, c_int, c_long, c_double, c_double, c_double, c_long, c_long, c_int, c_int, c_double,
+                                  P, P, c_size_t, P]),
+    "ddsp_hip_pool1d": (c_int, [P, c_int, c_long, c_int, c_int, P, P]),
 }
 
 MODE_ROLL, MODE_HANN, MODE_DYNAMIC = 0, 1, 2

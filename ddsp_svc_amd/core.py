@@ -43,6 +43,34 @@ def ir_table(n_mag, device):
     return tab
 
 
+def _pool1d(x, kernel_size, median, name):
+    k = int(kernel_size)
+    if x.dim() != 2 or x.dtype != torch.float32:
+        raise ValueError("%s: x must be a float32 [B, N] tensor (got %s %s)" % (name, x.dtype, tuple(x.shape)))
+    if not 1 <= k <= 16:
+        raise ValueError("%s: kernel_size must be in 1 .. 16 (got %d)" % (name, k))
+    B, N = x.shape
+    if N <= k // 2:
+        raise ValueError("%s: the reflection of kernel_size %d needs more than %d samples (got %d)" % (name, k, k // 2, N))
+    _ffi.check_device(x)
+    x = x.contiguous()
+    y = torch.empty_like(x)
+    _ffi.check(_ffi.lib().ddsp_hip_pool1d(ptr(x), B, N, k, int(median), ptr(y), _ffi.stream_of(x)))
+    return y
+
+
+def MaskedAvgPool1d(x, kernel_size):
+    """core.py:8-37: the mean over ``kernel_size`` reflect-padded samples of the values that are not NaN (0 where there is
+    none).  ``x [B, N]`` float32, kernel sizes 1 .. 16; the sum in float64, one rounding."""
+    return _pool1d(x, kernel_size, False, "MaskedAvgPool1d")
+
+
+def MedianPool1d(x, kernel_size):
+    """core.py:39-45: element ``(kernel_size - 1) // 2`` of each sorted reflect-padded window (NaN sorts last, as
+    ``torch.sort``).  ``x [B, N]`` float32, kernel sizes 1 .. 16."""
+    return _pool1d(x, kernel_size, True, "MedianPool1d")
+
+
 def get_fft_size(frame_size, ir_size, power_of_2=True):
     """core.py:47-63 (kept for API parity; the HIP path has no FFT size)."""
     convolved = ir_size + frame_size - 1

@@ -5,6 +5,7 @@
 #include "philox.h"
 #include "splice.h"
 #include "resample.h"
+#include "frame_features.h"
 #include <atomic>
 #include <stdio.h>
 #include <mutex>
@@ -1378,6 +1379,67 @@ int ddsp_hip_resample(const float* x, long ldx, long sx, int B, long L, float* y
   if (table_bytes < resample::tap_section(resample::tiles_of(new_))) return DDSP_HIP_EWS;
   if (reinterpret_cast<uintptr_t>(table) & 15) return DDSP_HIP_EINVAL;
   launch_resample(x, ldx, sx, B, L, y, ldy, table, orig, new_, width, S(stream));
+  return finish();
+}
+
+int ddsp_hip_volume(const float* audio, long ld, int B, long T, int hop, float* volume, void* stream) {
+  if (B < 0 || T < 1 || hop < 1 || ld < 0) return DDSP_HIP_EINVAL;
+  if (T <= ((long)hop + 1) / 2 || T > (1L << 40) || B > 65535) return DDSP_HIP_ESHAPE;   // the reflection needs that many samples
+  if (B > 1 && ld < T) return DDSP_HIP_EINVAL;
+  if (B == 0) return 0;
+  if (!audio || !volume) return DDSP_HIP_EINVAL;
+  launch_volume(audio, ld, B, T, hop, volume, S(stream));
+  return finish();
+}
+
+int ddsp_hip_gate(const float* signal, long ld_signal, const float* volume, int B, long F, int block, float threshold, int dilate,
+                  float* out, long ld_out, void* stream) {
+  if (B < 0 || F < 1 || block < 1 || dilate < 0 || !(threshold == threshold)) return DDSP_HIP_EINVAL;
+  if (dilate > features::kMaxDilate || F > (1L << 40) / block || B > 65535) return DDSP_HIP_ESHAPE;
+  if (B > 1 && (ld_signal < F * block || ld_out < F * block)) return DDSP_HIP_EINVAL;
+  if (B == 0) return 0;
+  if (!signal || !volume || !out) return DDSP_HIP_EINVAL;
+  launch_gate(signal, ld_signal, volume, B, F, block, threshold, dilate, out, ld_out, S(stream));
+  return finish();
+}
+
+int ddsp_hip_decode_salience(const float* hidden, long rows, const long long* center, float thred, float* f0, void* stream) {
+  if (rows < 0 || !(thred == thred)) return DDSP_HIP_EINVAL;
+  if (rows > (1L << 32)) return DDSP_HIP_ESHAPE;
+  if (rows == 0) return 0;
+  if (!hidden || !f0) return DDSP_HIP_EINVAL;
+  launch_salience(hidden, rows, center, thred, f0, S(stream));
+  return finish();
+}
+
+size_t ddsp_hip_f0_track_workspace_bytes(int B, long N, long n_frames) {
+  if (B < 1 || N < 1 || n_frames < 1 || N > (1L << 30) || n_frames > (1L << 30)) return 0;
+  return f0_track_ws_bytes(B, N, n_frames);
+}
+
+int ddsp_hip_f0_track(const float* f0_src, long ld, int B, long N, double src_period, double hop, double sample_rate,
+                      long n_frames, long start_frame, int mode, int uv_interp, double f0_min, float* out, void* ws,
+                      size_t ws_bytes, void* stream) {
+  if (B < 0 || N < 1 || n_frames < 1 || start_frame < 0 || start_frame > n_frames) return DDSP_HIP_EINVAL;
+  if (!(src_period > 0.0) || !(hop > 0.0) || !(sample_rate > 0.0) || !(f0_min == f0_min)) return DDSP_HIP_EINVAL;
+  if (mode != DDSP_HIP_TRACK_LINEAR && mode != DDSP_HIP_TRACK_NEAREST) return DDSP_HIP_EINVAL;
+  if (N > (1L << 30) || n_frames > (1L << 30)) return DDSP_HIP_ESHAPE;
+  if (B > 1 && ld < N) return DDSP_HIP_EINVAL;
+  if (B == 0) return 0;
+  if (!f0_src || !out) return DDSP_HIP_EINVAL;
+  if (!ws || ws_bytes < f0_track_ws_bytes(B, N, n_frames)) return DDSP_HIP_EWS;
+  if (reinterpret_cast<uintptr_t>(ws) & 15) return DDSP_HIP_EINVAL;
+  launch_f0_track(f0_src, ld, B, N, src_period, hop, sample_rate, n_frames, start_frame, mode == DDSP_HIP_TRACK_NEAREST ? 1 : 0,
+                  uv_interp ? 1 : 0, f0_min, out, ws, S(stream));
+  return finish();
+}
+
+int ddsp_hip_pool1d(const float* x, int B, long N, int k, int median, float* y, void* stream) {
+  if (B < 0 || N < 1) return DDSP_HIP_EINVAL;
+  if (k < 1 || k > features::kMaxPool || N <= k / 2 || N > (1L << 40) || B > 65535) return DDSP_HIP_ESHAPE;   // reflect: pad < N
+  if (B == 0) return 0;
+  if (!x || !y || x == y) return DDSP_HIP_EINVAL;
+  launch_pool1d(x, B, N, k, median ? 1 : 0, y, S(stream));
   return finish();
 }
 

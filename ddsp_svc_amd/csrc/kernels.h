@@ -191,4 +191,14 @@ size_t resample_table_bytes(const float* bank, int o, int n, int K);
 bool resample_table(const float* bank, int o, int n, int K, void* out, size_t bytes);
 void launch_resample(const float* x, long ldx, long sx, int B, long L, float* y, long ldy, const void* table, int o, int n,
                      int w, hipStream_t st);
+// the frame features of the real-time path (frame_features.h, compiled into api.hip): volume, gate, salience decode, F0 track, pools.
+// One launch each, no allocation; the track's ws: f0_track_ws_bytes(B, N, n_frames), 16-byte aligned
+size_t f0_track_ws_bytes(int B, long N, long n_frames);
+void launch_volume(const float* audio, long ld, int B, long T, int hop, float* vol, hipStream_t st);
+void launch_gate(const float* sig, long ld_s, const float* vol, int B, long F, int block, float thr, int dilate, float* out,
+                 long ld_o, hipStream_t st);
+void launch_salience(const float* hidden, long rows, const long long* center, float thred, float* f0, hipStream_t st);
+void launch_f0_track(const float* src, long ld, int B, long N, double period, double hop, double sr, long n_frames, long start,
+                     int nearest, int uv_interp, double f0_min, float* out, void* ws, hipStream_t st);
+void launch_pool1d(const float* x, int B, long N, int k, int median, float* y, hipStream_t st);
 }  // namespace ddsp

@@ -471,6 +471,51 @@ int ddsp_hip_resample_table(const float* bank, int orig, int new_, int K, void* 
 int ddsp_hip_resample(const float* x, long ldx, long sx, int B, long L, float* y, long ldy, const void* table,
                       size_t table_bytes, int orig, int new_, int width, void* stream);
 
+/* The frame features of the real-time path and the silence gate between them (ddsp/vocoder.py:104-157, gui.py:114-118 and :134,
+ * encoder/rmvpe/utils.py:106-121, ddsp/core.py:8-45).  These entry points came after version 165 without a version step: a caller
+ * that must run against older builds looks them up by name (dlsym) before use.  One launch each on the caller's stream, no
+ * allocation, no synchronisation.  Rows of a [B, n] argument are `ld` floats apart (ld >= n when B > 1); outputs without a stride
+ * are contiguous.  B = 0 is a no-op.
+ *
+ * ddsp_hip_volume: volume[b, f] = sqrt(mean(pad(audio[b]^2)[f hop : (f + 1) hop])), f < F = T / hop + 1, the pad numpy's `reflect`
+ * by (hop / 2, (hop + 1) / 2); float64 sums of the exact squares, one rounding to float32.  T <= (hop + 1) / 2: DDSP_HIP_ESHAPE.
+ *
+ * ddsp_hip_gate: out[b, i] = signal[b, i] * m, i < F block, m = mask[f] + (mask[f + 1] - mask[f]) r / block (f = i / block,
+ * r = i mod block, mask[F] = mask[F - 1]: ddsp/core.py upsample), mask[f] = max over |g - f| <= dilate (edge frames repeated) of
+ * volume[b, g] > threshold.  threshold is LINEAR and already float32 -- (float)10^(dB / 20) -- and the comparison is a float32
+ * one.  Where mask[f] = mask[f + 1] the product is exact; on a ramp it is rounded once from float64.  out may be signal.
+ * 0 <= dilate <= 64 (DDSP_HIP_ESHAPE).
+ *
+ * ddsp_hip_decode_salience: hidden [rows, 360] -> f0 [rows] (to_local_average_f0): c = the first argmax of the row, or center[row]
+ * (int64) when center is not null; the mean of 20 i + 1997.3794084376191 cents over i in [c - 4, c + 5) clipped to [0, 360),
+ * weighted by hidden (float64 sums; 0 cents when the weights sum to 0); f0 = 10 * 2^(cents / 1200), 0 where the row maximum
+ * is < thred (a float32 comparison).
+ *
+ * ddsp_hip_f0_track: f0_src [B, N] on a grid of src_period seconds -> out [B, n_frames] on a grid of hop / sample_rate seconds
+ * behind start_frame zeros (F0_Extractor.extract).  Zeros are unvoiced.  DDSP_HIP_TRACK_LINEAR: unvoiced frames of a row that has
+ * a voiced one are filled by linear interpolation between the nearest voiced neighbours (edges held) and stored as float32; the
+ * fill and the unvoiced flag are retimed with np.interp's arithmetic in float64 (source times src_period * i, target times
+ * (hop / sample_rate) * k, slope * (x - xp[j]) + fp[j]; the last value held past the end) and the track is 0 where the retimed
+ * flag is > 0.5.  DDSP_HIP_TRACK_NEAREST: out = f0_src[min(rint(k hop / sample_rate / src_period), N - 1)], no fill.  With
+ * uv_interp the zeros of the result (the prefix included) are filled the same way in float64 and everything below f0_min is
+ * raised to it (an all-unvoiced row becomes f0_min).  One workgroup per row; N, n_frames <= 2^30.
+ * ws: ddsp_hip_f0_track_workspace_bytes(B, N, n_frames) bytes, 16-byte aligned (DDSP_HIP_EWS when short).
+ *
+ * ddsp_hip_pool1d: MaskedAvgPool1d (median = 0: the mean of the values that are not NaN, 0 when there is none; float64 sum) or
+ * MedianPool1d (median = 1: element (k - 1) / 2 of the sorted window, NaN last) of x [B, N] over k samples, reflect-padded by
+ * ((k - 1) / 2, k / 2).  1 <= k <= 16 and N > k / 2 (DDSP_HIP_ESHAPE); y must not be x. */
+#define DDSP_HIP_TRACK_LINEAR   0
+#define DDSP_HIP_TRACK_NEAREST  1
+int ddsp_hip_volume(const float* audio, long ld, int B, long T, int hop, float* volume, void* stream);
+int ddsp_hip_gate(const float* signal, long ld_signal, const float* volume, int B, long F, int block, float threshold, int dilate,
+                  float* out, long ld_out, void* stream);
+int ddsp_hip_decode_salience(const float* hidden, long rows, const long long* center, float thred, float* f0, void* stream);
+size_t ddsp_hip_f0_track_workspace_bytes(int B, long N, long n_frames);
+int ddsp_hip_f0_track(const float* f0_src, long ld, int B, long N, double src_period, double hop, double sample_rate,
+                      long n_frames, long start_frame, int mode, int uv_interp, double f0_min, float* out, void* ws,
+                      size_t ws_bytes, void* stream);
+int ddsp_hip_pool1d(const float* x, int B, long N, int k, int median, float* y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
