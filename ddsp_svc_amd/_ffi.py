@@ -107,6 +107,11 @@ SIGNATURES = {
     "ddsp_hip_f0_track": (c_int, [P, c_long, c_int, c_long, c_double, c_double, c_double, c_long, c_long, c_int, c_int, c_double,
                                   P, P, c_size_t, P]),
     "ddsp_hip_pool1d": (c_int, [P, c_int, c_long, c_int, c_int, P, P]),
+    "ddsp_hip_resblock1_tile": (c_int, [c_int, c_int]),
+    "ddsp_hip_resblock1_pack_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "ddsp_hip_resblock1_pack": (c_int, [P, P, c_int, c_int, c_int, P, c_size_t]),
+    "ddsp_hip_resblock1_workspace_bytes": (c_size_t, [c_int, c_int, c_long, c_int]),
+    "ddsp_hip_resblock1": (c_int, [P, P, P, c_size_t, c_int, c_int, c_long, c_int, P, c_int, P, c_float, P, c_size_t, P]),
 }
 
 MODE_ROLL, MODE_HANN, MODE_DYNAMIC = 0, 1, 2

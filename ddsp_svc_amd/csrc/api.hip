@@ -6,6 +6,7 @@
 #include "splice.h"
 #include "resample.h"
 #include "frame_features.h"
+#include "resblock.h"
 #include <atomic>
 #include <stdio.h>
 #include <mutex>
@@ -1440,6 +1441,44 @@ int ddsp_hip_pool1d(const float* x, int B, long N, int k, int median, float* y, 
   if (B == 0) return 0;
   if (!x || !y || x == y) return DDSP_HIP_EINVAL;
   launch_pool1d(x, B, N, k, median ? 1 : 0, y, S(stream));
+  return finish();
+}
+
+int ddsp_hip_resblock1_tile(int C, int k) { return resblock::shape_ok(C, k) ? resblock::tile_of(k) : 0; }
+
+size_t ddsp_hip_resblock1_pack_bytes(int C, int k, int pairs) { return resblock_pack_bytes(C, k, pairs); }
+
+int ddsp_hip_resblock1_pack(const float* w, const float* b, int C, int k, int pairs, void* packed, size_t packed_bytes) {
+  if (!w || !b || !packed || pairs < 1) return DDSP_HIP_EINVAL;
+  const size_t need = resblock_pack_bytes(C, k, pairs);
+  if (need == 0) return DDSP_HIP_ESHAPE;
+  if (packed_bytes < need) return DDSP_HIP_EWS;
+  resblock_pack(w, b, C, k, pairs, static_cast<float*>(packed));
+  return 0;
+}
+
+size_t ddsp_hip_resblock1_workspace_bytes(int B, int C, long T, int pairs) {
+  if (B < 0 || T < 1 || pairs < 1 || pairs > resblock::kMaxPairs || (C != 16 && C != 32 && C != 64) || T > (1L << 40)) return 0;
+  return resblock_ws_bytes(B, C, T, pairs);
+}
+
+int ddsp_hip_resblock1(const float* x, float* y, const void* packed, size_t packed_bytes, int B, int C, long T, int k,
+                       const int* dilations, int pairs, const float* acc_in, float scale, void* ws, size_t ws_bytes,
+                       void* stream) {
+  if (B < 0 || T < 1 || pairs < 1 || !dilations || !(scale == scale)) return DDSP_HIP_EINVAL;
+  if (!resblock::shape_ok(C, k) || pairs > resblock::kMaxPairs || T > (1L << 40)) return DDSP_HIP_ESHAPE;
+  for (int p = 0; p < pairs; ++p) {
+    if (dilations[p] < 1) return DDSP_HIP_EINVAL;
+    if (!resblock::dilation_ok(C, k, dilations[p])) return DDSP_HIP_ESHAPE;    // its x image would not fit in LDS
+  }
+  if (B == 0) return 0;
+  if (!x || !y || !packed || x == y || acc_in == x) return DDSP_HIP_EINVAL;
+  if (packed_bytes < resblock_pack_bytes(C, k, pairs)) return DDSP_HIP_EWS;
+  const size_t need = resblock_ws_bytes(B, C, T, pairs);
+  if (need && (!ws || ws_bytes < need)) return DDSP_HIP_EWS;
+  if ((reinterpret_cast<uintptr_t>(packed) & 3) || (reinterpret_cast<uintptr_t>(ws) & 3)) return DDSP_HIP_EINVAL;
+  launch_resblock1(x, y, static_cast<const float*>(packed), B, C, T, k, dilations, pairs, acc_in, scale, static_cast<float*>(ws),
+                   S(stream));
   return finish();
 }
 

@@ -1,0 +1,266 @@
+"""The residual blocks of the NSF-HiFiGAN generator (``nsf_hifigan.models.ResBlock1`` and the sum over the blocks of an
+upsampling stage in ``Generator.forward``) on HIP: csrc/resblock.h, one launch per conv pair, both convolutions of a pair as
+f32 MFMA GEMMs with the intermediate in LDS, and the ``xs / num_kernels`` sum folded into the last launch of each block.
+
+  resblock1                  the functional form: ``x [B, C, T]``, one ``(w1, b1, w2, b2)`` per pair, the dilations
+  mrf_stage                  ``sum(block_j(x)) / len(blocks)`` of one stage, accumulated and divided in the kernels' epilogue
+  patch_reference_generator  rebinds ``ResBlock1.forward`` and ``Generator.forward`` of an importable reference checkout
+  unpatch_reference_generator
+
+Dispatch (``hip_eligible``): a float32 tensor on the GPU, no gradient needed, C in {16, 32, 64}, k in {3, 7, 11}, dilations the
+kernel's LDS image holds, and plain ``Conv1d`` weights -- every conv of the block has had ``remove_weight_norm`` applied (the
+weight-norm hook recomputes ``weight`` in a forward pre-hook, which a call that bypasses ``Conv1d.forward`` would never run).
+Everything else -- 128 / 256 channels, ``ResBlock2``, training, CPU tensors -- takes the reference's own forward unchanged.
+``TORCH_FASTER`` lists the (C, k) the measurements on one MI355X (tools/resblock_bench.py) found faster as the
+torch op chain: those are routed to it as well.
+"""
+import ctypes
+import threading
+
+import torch
+import torch.nn.functional as F
+
+from . import _ffi
+
+CHANNELS = (16, 32, 64)
+KERNEL_SIZES = (3, 7, 11)
+LRELU_SLOPE = 0.1
+# (C, k) -> the number of columns T below which the same-GPU torch chain was measured faster (None: at every T)
+TORCH_FASTER = {}
+
+_LOCK = threading.Lock()
+_PACKED = {}                                           # key of the weights -> (versions, device table, the tensors kept alive)
+_PACKED_MAX = 256
+_WS = {}                                               # device -> the hand-over buffer between pairs, grown on demand and kept
+CALLS = {"hip": 0, "reference": 0}                     # dispatch counters (tests and tools read them)
+
+
+def tile(C, k):
+    """output columns per workgroup (``ddsp_hip_resblock1_tile``): the tests place T around its multiples"""
+    return int(_ffi.lib().ddsp_hip_resblock1_tile(C, k))
+
+
+def _flat(weights):
+    return [t for pair in weights for t in pair]
+
+
+def _packed(weights, C, k, device):
+    """the kernel's weight table on ``device``: packed on the host once per set of weight tensors, found again by their
+    ``data_ptr`` and rebuilt when one of them was written in place (``_version``)"""
+    flat = _flat(weights)
+    key = (str(device), C, k) + tuple(t.data_ptr() for t in flat)
+    versions = tuple(t._version for t in flat)
+    hit = _PACKED.get(key)
+    if hit is not None and hit[0] == versions:
+        return hit[1]
+    lib = _ffi.lib()
+    pairs = len(weights)
+    with torch.no_grad():
+        w = torch.stack([t.detach().to("cpu", torch.float32) for pair in weights for t in (pair[0], pair[2])]).contiguous()
+        b = torch.stack([t.detach().to("cpu", torch.float32) for pair in weights for t in (pair[1], pair[3])]).contiguous()
+    nbytes = int(lib.ddsp_hip_resblock1_pack_bytes(C, k, pairs))
+    if nbytes == 0:
+        raise ValueError("resblock1: C = %d, k = %d, %d pairs is outside the kernel's range" % (C, k, pairs))
+    host = torch.empty(nbytes // 4, dtype=torch.float32)
+    _ffi.check(lib.ddsp_hip_resblock1_pack(w.data_ptr(), b.data_ptr(), C, k, pairs, host.data_ptr(), nbytes))
+    table = host.to(device)
+    with _LOCK:
+        while len(_PACKED) >= _PACKED_MAX:
+            _PACKED.pop(next(iter(_PACKED)))
+        _PACKED[key] = (versions, table, flat)         # the tensors stay alive, so a data_ptr cannot come back as another's
+    return table
+
+
+def _workspace(nbytes, device):
+    ws = _WS.get(device)
+    if ws is None or ws.numel() * 4 < nbytes:
+        ws = _WS[device] = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=device)
+    return ws
+
+
+def release_workspace():
+    """drop the cached hand-over buffers (2 [B, C, T] activations per device at the largest shape seen)"""
+    _WS.clear()
+
+
+def shape_ok(C, k, dilations):
+    """what the kernel takes: the x image of a tile, C rows of 128 + (k - 1) d columns padded to 16 mod 32, within 64 KB"""
+    if C not in CHANNELS or k not in KERNEL_SIZES or not 1 <= len(dilations) <= 8:
+        return False
+    return all(int(d) >= 1 and C * ((112 + (k - 1) * int(d) + 31) // 32 * 32 + 16) <= 16384 for d in dilations)
+
+
+def resblock1(x, weights, dilations, acc=None, scale=None, out=None):
+    """``ResBlock1.forward`` on the HIP kernel: ``x [B, C, T]`` float32, ``weights`` one ``(w1 [C, C, k], b1 [C], w2, b2)`` per
+    pair, ``dilations`` conv 1's dilation per pair.  Returns ``(acc + block(x)) / scale``: ``acc`` (optional, same shape) may
+    be ``out``; ``scale`` None means no division.  No synchronisation; the only allocation is the result (when ``out`` is
+    None) once the weight table and the hand-over buffer of this shape exist."""
+    _ffi.check_device(x, acc, out)
+    if x.dtype != torch.float32 or x.dim() != 3:
+        raise ValueError("resblock1: x must be a float32 [B, C, T] tensor")
+    B, C, T = x.shape
+    k = weights[0][0].shape[-1]
+    if len(weights) != len(dilations) or not shape_ok(C, k, dilations):
+        raise ValueError("resblock1: C = %d, k = %d, dilations %s is outside the kernel's range" % (C, k, tuple(dilations)))
+    for w1, b1, w2, b2 in weights:
+        if tuple(w1.shape) != (C, C, k) or tuple(w2.shape) != (C, C, k) or tuple(b1.shape) != (C,) or tuple(b2.shape) != (C,):
+            raise ValueError("resblock1: weights must be [C, C, k] and biases [C]")
+    if T < 1:
+        raise ValueError("resblock1: T must be positive")
+    x = x.contiguous()
+    y = torch.empty_like(x) if out is None else out
+    if acc is not None and (acc.shape != x.shape or acc.dtype != torch.float32 or not acc.is_contiguous()):
+        raise ValueError("resblock1: acc must be a contiguous float32 tensor of x's shape")
+    if not y.is_contiguous() or y.shape != x.shape or y.dtype != torch.float32:
+        raise ValueError("resblock1: out must be a contiguous float32 tensor of x's shape")
+    if B == 0:
+        return y
+    lib = _ffi.lib()
+    table = _packed(weights, C, k, x.device)
+    pairs = len(dilations)
+    nws = int(lib.ddsp_hip_resblock1_workspace_bytes(B, C, T, pairs))
+    ws = _workspace(nws, x.device) if nws else None
+    dil = (ctypes.c_int * pairs)(*[int(d) for d in dilations])
+    CALLS["hip"] += 1
+    _ffi.check(lib.ddsp_hip_resblock1(x.data_ptr(), y.data_ptr(), table.data_ptr(), table.numel() * 4, B, C, T, k,
+                                      ctypes.addressof(dil), pairs, _ffi.ptr(acc), 0.0 if scale is None else float(scale),
+                                      _ffi.ptr(ws), nws, _ffi.stream_of(x)))
+    return y
+
+
+def mrf_stage(x, blocks):
+    """one stage's ``xs = block_0(x); xs += block_j(x); xs / len(blocks)`` with ``blocks`` a list of ``(weights, dilations)``:
+    the running sum is the epilogue's ``acc`` (in place), the division the last block's ``scale``"""
+    xs = None
+    for j, (weights, dilations) in enumerate(blocks):
+        xs = resblock1(x, weights, dilations, acc=xs, scale=len(blocks) if j == len(blocks) - 1 else None, out=xs)
+    return xs
+
+
+# ---- the reference's modules --------------------------------------------------------------------------------------------------
+
+def _plain_conv(c, C, k, d):
+    """a Conv1d the kernel can stand in for: C -> C channels, k taps, dilation d, 'same' zero padding, and a ``weight`` that is
+    a plain parameter (no weight-norm hook or parametrization left on it)"""
+    if not isinstance(c, torch.nn.Conv1d) or not isinstance(c._parameters.get("weight"), torch.Tensor):
+        return False
+    if any(type(h).__name__ == "WeightNorm" for h in c._forward_pre_hooks.values()):
+        return False
+    if c._forward_pre_hooks or c._forward_hooks:       # any other hook expects Conv1d.forward to run
+        return False
+    pad = c.padding if isinstance(c.padding, tuple) else (c.padding,)
+    return (c.in_channels == C and c.out_channels == C and c.kernel_size == (k,) and c.stride == (1,) and c.dilation == (d,)
+            and c.groups == 1 and c.padding_mode == "zeros" and pad == ((k * d - d) // 2,) and c.bias is not None
+            and c.weight.dtype == torch.float32)
+
+
+def _block_spec(block):
+    """``(weights, dilations)`` of a ResBlock1-shaped module (``convs1`` / ``convs2`` ModuleLists), or None"""
+    c1s, c2s = getattr(block, "convs1", None), getattr(block, "convs2", None)
+    if c1s is None or c2s is None or len(c1s) != len(c2s) or len(c1s) == 0:
+        return None
+    c0 = c1s[0]
+    if not isinstance(c0, torch.nn.Conv1d):
+        return None
+    C, k = c0.in_channels, c0.kernel_size[0]
+    dil = [c.dilation[0] if isinstance(c, torch.nn.Conv1d) else 0 for c in c1s]
+    if not shape_ok(C, k, dil):
+        return None
+    if not all(_plain_conv(a, C, k, d) and _plain_conv(b, C, k, 1) for a, b, d in zip(c1s, c2s, dil)):
+        return None
+    return [(a.weight, a.bias, b.weight, b.bias) for a, b in zip(c1s, c2s)], dil
+
+
+def _on_device(x):
+    try:
+        _ffi.check_device(x)
+    except RuntimeError:
+        return False
+    return True
+
+
+def hip_eligible(block, x):
+    """the ``(weights, dilations)`` to run ``block`` on ``x`` with the HIP kernel, or None: the reference's forward"""
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() != 3 or x.shape[-1] < 1 or not _on_device(x):
+        return None
+    spec = _block_spec(block)
+    if spec is None or x.shape[1] != spec[0][0][0].shape[0]:
+        return None
+    if torch.is_grad_enabled() and (x.requires_grad or any(t.requires_grad for t in _flat(spec[0]))):
+        return None
+    C, k = x.shape[1], spec[0][0][0].shape[-1]
+    if (C, k) in TORCH_FASTER and (TORCH_FASTER[(C, k)] is None or x.shape[-1] < TORCH_FASTER[(C, k)]):
+        return None
+    return spec
+
+
+def _reference_block_forward(block, x):
+    CALLS["reference"] += 1
+    ref = getattr(type(block), "_reference_forward", None)
+    if ref is not None:
+        return ref(block, x)
+    for c1, c2 in zip(block.convs1, block.convs2):     # a stand-in class without a forward of its own: the same chain
+        x = c2(F.leaky_relu(c1(F.leaky_relu(x, LRELU_SLOPE)), LRELU_SLOPE)) + x
+    return x
+
+
+def resblock_forward(block, x):
+    """the dispatcher bound as ``ResBlock1.forward``"""
+    spec = hip_eligible(block, x)
+    if spec is None:
+        return _reference_block_forward(block, x)
+    return resblock1(x, spec[0], spec[1])
+
+
+def stage_forward(blocks, x):
+    """the blocks of one stage, summed and divided by their number: through ``mrf_stage`` when every one is eligible,
+    otherwise block by block as the reference sums them"""
+    specs = [hip_eligible(b, x) for b in blocks]
+    if all(s is not None for s in specs):
+        return mrf_stage(x, specs)
+    xs = None
+    for b in blocks:
+        r = b(x)
+        xs = r if xs is None else xs.add_(r)
+    return xs / len(blocks)
+
+
+def patch_reference_generator():
+    """Route ``nsf_hifigan.models.ResBlock1.forward`` and the per-stage block sum of ``Generator.forward`` of an importable
+    reference checkout through the dispatchers above.  Idempotent; returns the module."""
+    import nsf_hifigan.models as nm
+    if hasattr(nm.ResBlock1, "_reference_forward"):
+        return nm
+    nm.ResBlock1._reference_forward = nm.ResBlock1.forward
+    nm.Generator._reference_forward = nm.Generator.forward
+    ref_generator_forward = nm.Generator.forward
+
+    def generator_forward(self, x, f0):
+        first = self.resblocks[0] if len(self.resblocks) else None
+        if (not isinstance(first, nm.ResBlock1) or not isinstance(x, torch.Tensor) or x.dtype != torch.float32
+                or not _on_device(x) or (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()))):
+            return ref_generator_forward(self, x, f0)
+        source = self.m_source(f0, self.upp).transpose(1, 2)
+        x = self.conv_pre(x)
+        n = self.num_kernels
+        for i, (up, noise_conv) in enumerate(zip(self.ups, self.noise_convs)):
+            x = up(F.leaky_relu(x, nm.LRELU_SLOPE)) + noise_conv(source)
+            x = stage_forward(self.resblocks[i * n:(i + 1) * n], x)
+        return torch.tanh(self.conv_post(F.leaky_relu(x)))
+
+    nm.ResBlock1.forward = resblock_forward
+    nm.Generator.forward = generator_forward
+    return nm
+
+
+def unpatch_reference_generator():
+    """Undo ``patch_reference_generator()``."""
+    import sys
+    nm = sys.modules.get("nsf_hifigan.models")
+    if nm is None:
+        return
+    for cls in (nm.ResBlock1, nm.Generator):
+        ref = cls.__dict__.get("_reference_forward")
+        if ref is not None:
+            cls.forward = ref
+            del cls._reference_forward

@@ -516,6 +516,30 @@ int ddsp_hip_f0_track(const float* f0_src, long ld, int B, long N, double src_pe
                       size_t ws_bytes, void* stream);
 int ddsp_hip_pool1d(const float* x, int B, long N, int k, int median, float* y, void* stream);
 
+/* NSF-HiFiGAN's ResBlock1 (nsf_hifigan/models.py:37-68) and the sum over the blocks of a stage (models.py:253-259), csrc/resblock.h.
+ * These entry points came after version 165 without a version step: a caller that must run against older builds looks them up
+ * by name (dlsym) before use.  C in {16, 32, 64}, k in {3, 7, 11} (DDSP_HIP_ESHAPE otherwise), x and y [B, C, T] contiguous.
+ *
+ * ddsp_hip_resblock1_tile: output columns per workgroup, 128 - (k - 1); 0 for a (C, k) the kernel does not take.
+ * ddsp_hip_resblock1_pack_bytes / _pack: HOST weights w [2 pairs][C][C][k] in the order convs1[0], convs2[0], convs1[1], ... and
+ * biases b [2 pairs][C] -> the table the kernel reads, written to HOST memory (the caller copies it to the device once and
+ * keeps it); 1 <= pairs <= 8.  0 bytes / DDSP_HIP_ESHAPE out of range, DDSP_HIP_EWS short.
+ * ddsp_hip_resblock1: for p < pairs, x <- conv1d(lrelu(conv1d(lrelu(x), w1_p, b1_p, dilation d_p)), w2_p, b2_p) + x with slope
+ * 0.1 and "same" zero padding of each conv's own input; then y = (acc_in + x) / scale: acc_in may be null (nothing added) or y
+ * itself, scale = 0 means no division (otherwise an IEEE division, as the reference's xs / num_kernels).  dilations: host ints,
+ * each >= 1 (DDSP_HIP_EINVAL) and small enough for the tile's input to fit in 64 KB of LDS: C (16 + 32 ceil((112 + (k - 1) d) / 32))
+ * <= 16384, i.e. d <= 11 at C = 64, k = 11 and more everywhere else (DDSP_HIP_ESHAPE).  T >= 1 (DDSP_HIP_EINVAL); B = 0 is a
+ * no-op.  One launch per pair (per 65 535 utterances), f32 MFMA, the intermediate of a pair stays in LDS; the pairs hand over
+ * through ws: ddsp_hip_resblock1_workspace_bytes(B, C, T, pairs) bytes (0 for one pair; DDSP_HIP_EWS when short).  x must not be
+ * y or acc_in.  No allocation, no synchronisation. */
+int ddsp_hip_resblock1_tile(int C, int k);
+size_t ddsp_hip_resblock1_pack_bytes(int C, int k, int pairs);
+int ddsp_hip_resblock1_pack(const float* w, const float* b, int C, int k, int pairs, void* packed, size_t packed_bytes);
+size_t ddsp_hip_resblock1_workspace_bytes(int B, int C, long T, int pairs);
+int ddsp_hip_resblock1(const float* x, float* y, const void* packed, size_t packed_bytes, int B, int C, long T, int k,
+                       const int* dilations, int pairs, const float* acc_in, float scale, void* ws, size_t ws_bytes,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif
