@@ -236,7 +236,15 @@ def ptr(t):
     return None if t is None else t.data_ptr()
 
 
-def check(code):
+MAX_BATCH = 65535                                              # workgroups a grid holds in y and z
+
+
+def check(code, batch=None):
+    """Raise for a non-zero return of the C ABI.  ``batch``: the call's utterance count, for the entries whose kernels put
+    the utterance on the grid's y axis and refuse more than 65 535 of them: the error then says so."""
     if code != 0:
+        if code == -3 and batch is not None and batch > MAX_BATCH:
+            raise ValueError("libddsp_hip: this entry takes at most %d utterances per call (got %d): split the batch"
+                             % (MAX_BATCH, batch))
         msg = lib().ddsp_hip_error_string(code)
         raise RuntimeError("libddsp_hip: %s (code %d)" % (msg.decode() if msg else "?", code))

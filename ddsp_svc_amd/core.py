@@ -55,7 +55,7 @@ def _pool1d(x, kernel_size, median, name):
     _ffi.check_device(x)
     x = x.contiguous()
     y = torch.empty_like(x)
-    _ffi.check(_ffi.lib().ddsp_hip_pool1d(ptr(x), B, N, k, int(median), ptr(y), _ffi.stream_of(x)))
+    _ffi.check(_ffi.lib().ddsp_hip_pool1d(ptr(x), B, N, k, int(median), ptr(y), _ffi.stream_of(x)), batch=B)
     return y
 
 
@@ -269,7 +269,7 @@ def _fft_convolve_forward(x, ir, impl):
     hop = T // F
     out = torch.empty(B, T, dtype=torch.float32, device=x.device)
     _ffi.check(_ffi.lib().ddsp_hip_fft_convolve(ptr(x), 0, ptr(ir), None, ptr(out), None, B, F, hop, N, int(impl),
-                                                _ffi.stream_of(x)))
+                                                _ffi.stream_of(x)), batch=B)
     return out
 
 
@@ -283,7 +283,7 @@ def fft_convolve_backward(grad_out, audio, impulse_response, need_audio_grad=Tru
     d_x = torch.empty_like(x) if need_audio_grad else None
     d_ir = torch.empty_like(ir)
     _ffi.check(_ffi.lib().ddsp_hip_fft_convolve_backward(ptr(x), 0, ptr(ir), ptr(g), ptr(d_x), ptr(d_ir), B, F, hop, N,
-                                                         _ffi.stream_of(x)))
+                                                         _ffi.stream_of(x)), batch=B)
     return d_x, d_ir
 
 
@@ -320,7 +320,7 @@ class FftConvolveAddFunction(torch.autograd.Function):
         out = torch.empty(B, T, dtype=torch.float32, device=x.device)
         plain = torch.empty_like(out)
         _ffi.check(_ffi.lib().ddsp_hip_fft_convolve(ptr(x), 0, ptr(ir), ptr(ad), ptr(out), ptr(plain), B, F, T // F, N, int(impl),
-                                                    _ffi.stream_of(x)))
+                                                    _ffi.stream_of(x)), batch=B)
         return out, plain
 
     @staticmethod

@@ -336,8 +336,9 @@ int launch_mel_czt(const float* audio, int B, int T, const float* tab, int n_new
     if (best < 0 || cost < best) { best = cost; g.span = sp; }
   }
   const float2* tb = reinterpret_cast<const float2*>(tab);
-  for (int b0 = 0; b0 < B; b0 += 65535) {                    // grid.y holds 65535 utterances
-    const int nb = B - b0 < 65535 ? B - b0 : 65535;
+  const int split = (int)batch_split();                      // grid.y holds 65535 utterances
+  for (int b0 = 0; b0 < B; b0 += split) {
+    const int nb = B - b0 < split ? B - b0 : split;
     const dim3 grid((unsigned)((frames + g.span - 1) / g.span), (unsigned)nb);
     const float* a = audio + (long)b0 * T;
     float* o = out + (long)b0 * sb;

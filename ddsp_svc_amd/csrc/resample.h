@@ -25,6 +25,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include <string.h>
+#include "tuning.h"
 
 namespace ddsp {
 namespace resample {
@@ -250,9 +251,10 @@ void launch_resample(const float* x, long ldx, long sx, int B, long L, float* y,
   a.op = G * o; a.np = np; a.w = w;
   if (a.T == 0) return;
   const long mt = (a.M + kTM - 1) / kTM;
-  for (long b0 = 0; b0 < B; b0 += 65535) {
+  const long split = batch_split();
+  for (long b0 = 0; b0 < B; b0 += split) {
     a.b0 = b0;
-    const long nb = B - b0 < 65535 ? B - b0 : 65535;
+    const long nb = B - b0 < split ? B - b0 : split;
     hipLaunchKernelGGL(k_resample, dim3((unsigned)mt, (unsigned)tiles, (unsigned)nb), dim3(kThreads), 0, st, a);
   }
 }

@@ -29,6 +29,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include "tuning.h"
 
 namespace ddsp {
 namespace resblock {
@@ -150,9 +151,10 @@ template <int C, int K>
 inline void launch_pair_ck(Args a, int B, hipStream_t st) {
   const long tiles = (a.T + tile_of(K) - 1) / tile_of(K);
   const size_t lds = (size_t)C * a.rs * sizeof(float);
-  for (long b0 = 0; b0 < B; b0 += 65535) {
+  const long split = batch_split();
+  for (long b0 = 0; b0 < B; b0 += split) {
     a.b0 = b0;
-    const long nb = B - b0 < 65535 ? B - b0 : 65535;
+    const long nb = B - b0 < split ? B - b0 : split;
     hipLaunchKernelGGL((k_resblock_pair<C, K>), dim3((unsigned)tiles, (unsigned)nb), dim3(kThreads), lds, st, a);
   }
 }

@@ -10,7 +10,7 @@ enum Knob {
   KNOB_BLK_WPS = 0, KNOB_BLK_RUN, KNOB_BLK_PADLDS, KNOB_FFT_RUN, KNOB_STFT_WPS, KNOB_STFT_RUN, KNOB_MEL_WPS,
   KNOB_MEL_RUN, KNOB_FIR_MAX_SLOTS, KNOB_SINS_V1, KNOB_TAPS_GEMM, KNOB_STREAM_LAYOUT, KNOB_BLK_TURNS, KNOB_CZT_ROUNDS, KNOB_CZT_TURNS,
   KNOB_SINS_NOSKIP, KNOB_SMALL_PATH, KNOB_LANE_ROWS, KNOB_LANES, KNOB_FIR_BWD_DIRECT, KNOB_BWD_WPS, KNOB_TAPS_FULL,
-  KNOB_AP_BWD_SPLIT, KNOB_SINS_SEQ,
+  KNOB_AP_BWD_SPLIT, KNOB_SINS_SEQ, KNOB_BATCH_SPLIT,
   KNOB_COUNT
 };
 
@@ -20,5 +20,15 @@ constexpr long kSmallRows = 4096;
 long knob(Knob k);                       // current value; 0 = unset (use the built-in default)
 int knob_set(const char* name, long v);  // 0 on success, -1 for an unknown name
 long knob_get(const char* name);         // value, or -1 for an unknown name
+
+// A grid holds 65 535 workgroups in y and z.  The launchers that put the utterance index there and take a larger batch
+// (resblock.h, resample.h, mel_czt.hip) go through it in chunks of this many utterances, each launch starting at a base
+// utterance.  Test knob BATCH_SPLIT = 1 .. 65 535: chunks of that size, so that a handful of utterances reach the second chunk;
+// 0 (unset) or any other value: 65 535.
+constexpr long kMaxGridYZ = 65535;
+inline long batch_split() {
+  const long v = knob(KNOB_BATCH_SPLIT);
+  return v >= 1 && v <= kMaxGridYZ ? v : kMaxGridYZ;
+}
 
 }  // namespace ddsp

@@ -64,7 +64,7 @@ def volume(audio, hop_size):
         raise ValueError("volume: the reflection of hop %d needs more than %d samples (got %d)" % (hop, (hop + 1) // 2, T))
     _ffi.check_device(a2)
     out = torch.empty(B, T // hop + 1, dtype=torch.float32, device=a2.device)
-    _ffi.check(_ffi.lib().ddsp_hip_volume(a2.data_ptr(), _ld(a2), B, T, hop, out.data_ptr(), _ffi.stream_of(a2)))
+    _ffi.check(_ffi.lib().ddsp_hip_volume(a2.data_ptr(), _ld(a2), B, T, hop, out.data_ptr(), _ffi.stream_of(a2)), batch=B)
     return out[0] if one else out
 
 
@@ -108,7 +108,7 @@ def gate(signal, volume, threshold_db, block_size, dilate=4, out=None):
                              % (name, tuple(t.stride())))
     _ffi.check_device(s2, v2, o2)
     v2 = v2.contiguous()
-    _ffi.check(_ffi.lib().ddsp_hip_gate(s2.data_ptr(), _ld(s2), v2.data_ptr(), B, F, block, threshold_of(threshold_db), d, o2.data_ptr(), _ld(o2), _ffi.stream_of(s2)))
+    _ffi.check(_ffi.lib().ddsp_hip_gate(s2.data_ptr(), _ld(s2), v2.data_ptr(), B, F, block, threshold_of(threshold_db), d, o2.data_ptr(), _ld(o2), _ffi.stream_of(s2)), batch=B)
     return out
 
 
@@ -228,7 +228,7 @@ class StreamingFeatures:
 
     def volume(self, audio):
         one, ld = self._check(audio, self.T, "audio")
-        _ffi.check(self._lib.ddsp_hip_volume(audio.data_ptr(), ld, self.B, self.T, self.hop, self.vol.data_ptr(), self._stream))
+        _ffi.check(self._lib.ddsp_hip_volume(audio.data_ptr(), ld, self.B, self.T, self.hop, self.vol.data_ptr(), self._stream), batch=self.B)
         return self._vol1 if one else self.vol
 
     def track(self, f0_src):
@@ -241,7 +241,7 @@ class StreamingFeatures:
     def gate_(self, signal):
         _, ld = self._check(signal, self.F * self.block, "signal")
         _ffi.check(self._lib.ddsp_hip_gate(signal.data_ptr(), ld, self.vol.data_ptr(), self.B, self.F, self.block, self._thr,
-                                           self.dilate, signal.data_ptr(), ld, self._stream))
+                                           self.dilate, signal.data_ptr(), ld, self._stream), batch=self.B)
         return signal
 
 

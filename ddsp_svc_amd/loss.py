@@ -47,7 +47,7 @@ class _SpectralLossFunction(torch.autograd.Function):
         norms = torch.empty(B, 2, dtype=torch.float32, device=dev)
         loss = torch.empty((), dtype=torch.float32, device=dev)
         _ffi.check(lib.ddsp_hip_spectral_loss(ptr(st), ptr(sp), B, per, float(inv_window_norm), float(eps), float(alpha),
-                                              ptr(scratch), nbytes, ptr(norms), ptr(loss), _ffi.stream_of(st)))
+                                              ptr(scratch), nbytes, ptr(norms), ptr(loss), _ffi.stream_of(st)), batch=B)
         ctx.save_for_backward(st, sp, norms)
         ctx.cfg = (float(inv_window_norm), float(eps), float(alpha))
         return loss
@@ -67,7 +67,7 @@ class _SpectralLossFunction(torch.autograd.Function):
             d = torch.empty_like(sp)                                 # same dense layout as the saved spectra
             _ffi.check(lib.ddsp_hip_spectral_loss_backward(ptr(st), ptr(sp), B, per, ptr(norms), inv_wn, eps, alpha,
                                                            ptr(go), 1 if which == 0 else 0, ptr(d),
-                                                           _ffi.stream_of(sp)))
+                                                           _ffi.stream_of(sp)), batch=B)
             grads[which] = d
         return grads[0], grads[1], None, None, None
 
@@ -132,7 +132,7 @@ class _WaveLossFunction(torch.autograd.Function):
         loss = torch.empty((), dtype=torch.float32, device=dev)
         _ffi.check(lib.ddsp_hip_stft_loss(ptr(xt), ptr(xp), B, T, xt.stride(0), n_fft, hop, ptr(tables),
                                           float(inv_window_norm), float(eps), float(alpha), ptr(scratch), nbytes,
-                                          ptr(spec[0]), ptr(spec[1]), ptr(norms), ptr(loss), _ffi.stream_of(xt)))
+                                          ptr(spec[0]), ptr(spec[1]), ptr(norms), ptr(loss), _ffi.stream_of(xt)), batch=B)
         ctx.save_for_backward(spec, norms, tables)
         ctx.cfg = (B, T, int(n_fft), int(hop), float(inv_window_norm), float(eps), float(alpha))
         return loss
@@ -181,7 +181,7 @@ class _RandomScaleWaveLossFunction(torch.autograd.Function):
             spec = torch.empty(2, B, frames, n // 2 + 1, dtype=torch.complex64, device=dev)
             _ffi.check(lib.ddsp_hip_stft_loss(ptr(xt), ptr(xp), B, T, xt.stride(0), n, hop, ptr(tab), inv_wn, float(eps),
                                               float(alpha), ptr(scratch), nbytes, ptr(spec[0]), ptr(spec[1]),
-                                              ptr(norms[i]), ptr(losses[i:]), _ffi.stream_of(xt)))
+                                              ptr(norms[i]), ptr(losses[i:]), _ffi.stream_of(xt)), batch=B)
             specs.append(spec)
         ctx.save_for_backward(norms, *specs, *tables)
         ctx.cfg = (B, T, tuple(scales), float(eps), float(alpha))

@@ -112,7 +112,7 @@ class _MelSpectrogram(torch.autograd.Function):
         _ffi.check(lib.ddsp_hip_mel_spectrogram_backward(ptr(a), B, T, ptr(window), n_fft, ctx.hop, ptr(mel_basis), ptr(band),
                                                          ptr(packed), packed.numel(), ptr(bins), mel_basis.shape[0], ctx.clip,
                                                          ptr(g), g.stride(0), g.stride(1), g.stride(2), ptr(dx), ptr(ws),
-                                                         nbytes, _ffi.stream_of(a)))
+                                                         nbytes, _ffi.stream_of(a)), batch=B)
         return dx.to(ctx.dtype), None, None, None, None, None, None, None
 
 

@@ -46,14 +46,14 @@ def sine_source(f0, upp, sampling_rate, weight, bias, rand_ini, noise, sine_amp=
         _ffi.check(_ffi.lib().ddsp_hip_sine_source_drawn(ptr(f0c), B, L, upp, float(sampling_rate), ptr(ri), int(noise_seed),
                                                          int(noise_offset), ptr(w), ptr(bb), dim, float(sine_amp),
                                                          float(noise_std), float(voiced_threshold), ptr(acc), ptr(out),
-                                                         _ffi.stream_of(f0c)))
+                                                         _ffi.stream_of(f0c)), batch=B)
         return out
     nz = c(noise)
     if nz.numel() != B * L * upp * dim:
         raise ValueError("noise must be [B, L*upp, dim]")
     _ffi.check(_ffi.lib().ddsp_hip_sine_source(ptr(f0c), B, L, upp, float(sampling_rate), ptr(ri), ptr(nz), ptr(w), ptr(bb),
                                                dim, float(sine_amp), float(noise_std), float(voiced_threshold), ptr(acc),
-                                               ptr(out), _ffi.stream_of(f0c)))
+                                               ptr(out), _ffi.stream_of(f0c)), batch=B)
     return out
 
 

@@ -94,7 +94,7 @@ def sola_splice(audio, sola_buffer, fade_in, fade_out, block_frame, crossfade_fr
     ws, need = _workspace(B, C, use_phase_vocoder, dev)
     _ffi.check(_ffi.lib().ddsp_hip_sola_splice(
         a2.data_ptr(), a2.stride(0) if B > 1 else L, B, L, Bf, C, S, D, buf.data_ptr(), new_buf.data_ptr(), fi.data_ptr(),
-        fo.data_ptr(), int(bool(use_phase_vocoder)), out.data_ptr(), shift.data_ptr(), ws.data_ptr(), need, _ffi.stream_of(a2)))
+        fo.data_ptr(), int(bool(use_phase_vocoder)), out.data_ptr(), shift.data_ptr(), ws.data_ptr(), need, _ffi.stream_of(a2)), batch=B)
     if one:
         return out[0], new_buf[0], shift[0]
     return out, new_buf, shift
@@ -166,7 +166,7 @@ class StreamingSplice:
             audio.data_ptr(), L if one or self.B == 1 else audio.stride(0), self.B, L, self.block_frame, self.crossfade_frame,
             self.sola_search_frame, self.last_delay_frame, self._ptrs[c], self._ptrs[1 - c], self.fade_in.data_ptr(),
             self.fade_out.data_ptr(), int(self.use_phase_vocoder), self.out.data_ptr(), self.shift.data_ptr(), self._ws.data_ptr(),
-            self._need, self._stream))
+            self._need, self._stream), batch=self.B)
         self._cur = 1 - c
         return (self._out1, self._shift1) if one else (self.out, self.shift)
 

@@ -311,7 +311,7 @@ def _fir_bwd(x, x_is_u01, taps, grad, need_dx):
     d_taps = torch.empty(B, F, N, dtype=torch.float32, device=x.device)
     d_x = torch.empty(B, T, dtype=torch.float32, device=x.device) if need_dx else None
     _ffi.check(_ffi.lib().ddsp_hip_fft_convolve_backward(ptr(x), int(x_is_u01), ptr(taps), ptr(grad), ptr(d_x), ptr(d_taps),
-                                                         B, F, T // F, N, _ffi.stream_of(x)))
+                                                         B, F, T // F, N, _ffi.stream_of(x)), batch=B)
     return d_x, d_taps
 
 

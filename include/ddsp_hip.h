@@ -12,7 +12,15 @@
  *     hipError_t if a launch failed; ddsp_hip_error_string() decodes both;
  *   - tensors are float32 row-major; B = utterances, F = frames, hop = samples per frame,
  *     T = F*hop; control tensors take a row stride `ld` (floats between consecutive frames) so
- *     the torch.split views of Unit2Control's output can be passed without a copy.
+ *     the torch.split views of Unit2Control's output can be passed without a copy;
+ *   - more than 65 535 utterances in one call (a grid's limit in y and z): ddsp_hip_resblock1, ddsp_hip_resample and
+ *     ddsp_hip_mel_shifted_spectrogram split the batch into launches of 65 535; ddsp_hip_fast_source and
+ *     ddsp_hip_combsubsuperfast_synth run their exciter on a flat grid then; ddsp_hip_sine_source(_drawn),
+ *     ddsp_hip_spectral_loss(_backward), ddsp_hip_stft_loss(_backward), ddsp_hip_mel_spectrogram_backward,
+ *     ddsp_hip_sola_splice, ddsp_hip_volume, ddsp_hip_gate, ddsp_hip_pool1d, ddsp_hip_fft_convolve with
+ *     DDSP_HIP_FIR_SIMPLE and ddsp_hip_fft_convolve_backward at shapes only its direct form takes (hop != 512 or
+ *     N > 1022) return DDSP_HIP_ESHAPE before any launch; the other entries index utterances
+ *     on a flat grid.
  */
 #ifndef DDSP_HIP_H
 #define DDSP_HIP_H
@@ -64,7 +72,9 @@ const char* ddsp_hip_error_string(int code);
  * filter's tap rows whole, [B,F,N], instead of their first N/2 + 1 taps -- an even response; same bits either way),
  * AP_BWD_SPLIT (1 = ddsp_hip_combsub_tail_backward runs the all-pass activation's adjoint as a launch of its own instead of
  * in the last stage of the tap adjoint), SINS_SEQ (1 = the Sins tail's two filters as two launches instead of one whose workgroups
- * run the noise filter and then the all-pass filter over the same samples; same bits); the rest are run lengths. */
+ * run the noise filter and then the all-pass filter over the same samples; same bits), BATCH_SPLIT (test knob: 1 .. 65535 =
+ * the utterances per launch of the three entries that split a batch past the grid's 65 535, so that a handful of utterances
+ * reach a second launch; 0 or anything else = 65 535; same bits); the rest are run lengths. */
 int ddsp_hip_set_tuning(const char* name, long value);
 long ddsp_hip_get_tuning(const char* name);
 
