@@ -112,6 +112,12 @@ SIGNATURES = {
     "ddsp_hip_resblock1_pack": (c_int, [P, P, c_int, c_int, c_int, P, c_size_t]),
     "ddsp_hip_resblock1_workspace_bytes": (c_size_t, [c_int, c_int, c_long, c_int]),
     "ddsp_hip_resblock1": (c_int, [P, P, P, c_size_t, c_int, c_int, c_long, c_int, P, c_int, P, c_float, P, c_size_t, P]),
+    "ddsp_hip_upsample_stage_tile": (c_int, [c_int, c_int]),
+    "ddsp_hip_upsample_stage_pack_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "ddsp_hip_upsample_stage_pack": (c_int, [P, P, P, P, c_int, c_int, c_int, P, c_size_t]),
+    "ddsp_hip_upsample_stage": (c_int, [P, P, P, P, c_size_t, c_int, c_int, c_long, c_int, c_int, P]),
+    "ddsp_hip_output_head_tile": (c_int, [c_int]),
+    "ddsp_hip_output_head": (c_int, [P, P, P, c_float, P, c_int, c_int, c_long, P]),
 }
 
 MODE_ROLL, MODE_HANN, MODE_DYNAMIC = 0, 1, 2

@@ -7,6 +7,7 @@
 #include "resample.h"
 #include "frame_features.h"
 #include "resblock.h"
+#include "generator_tail.h"
 #include <atomic>
 #include <stdio.h>
 #include <mutex>
@@ -1479,6 +1480,45 @@ int ddsp_hip_resblock1(const float* x, float* y, const void* packed, size_t pack
   if ((reinterpret_cast<uintptr_t>(packed) & 3) || (reinterpret_cast<uintptr_t>(ws) & 3)) return DDSP_HIP_EINVAL;
   launch_resblock1(x, y, static_cast<const float*>(packed), B, C, T, k, dilations, pairs, acc_in, scale, static_cast<float*>(ws),
                    S(stream));
+  return finish();
+}
+
+int ddsp_hip_upsample_stage_tile(int Cout, int u) { return gentail::seam_shape_ok(Cout, u, 1) ? gentail::seam_tile(Cout, u) : 0; }
+
+size_t ddsp_hip_upsample_stage_pack_bytes(int Cout, int u, int s) { return upsample_stage_pack_bytes(Cout, u, s); }
+
+int ddsp_hip_upsample_stage_pack(const float* wu, const float* bu, const float* wn, const float* bn, int Cout, int u, int s,
+                                 void* packed, size_t packed_bytes) {
+  if (!wu || !bu || !wn || !bn || !packed) return DDSP_HIP_EINVAL;
+  const size_t need = upsample_stage_pack_bytes(Cout, u, s);
+  if (need == 0) return DDSP_HIP_ESHAPE;
+  if (packed_bytes < need) return DDSP_HIP_EWS;
+  upsample_stage_pack(wu, bu, wn, bn, Cout, u, s, static_cast<float*>(packed));
+  return 0;
+}
+
+int ddsp_hip_upsample_stage(const float* x, const float* src, float* y, const void* packed, size_t packed_bytes, int B, int Cout,
+                            long Tin, int u, int s, void* stream) {
+  if (B < 0 || Tin < 1) return DDSP_HIP_EINVAL;
+  if (!gentail::seam_shape_ok(Cout, u, s) || Tin > (1L << 30)) return DDSP_HIP_ESHAPE;
+  if (B == 0) return 0;
+  if (!x || !src || !y || !packed || x == y || src == y) return DDSP_HIP_EINVAL;
+  if (packed_bytes < upsample_stage_pack_bytes(Cout, u, s)) return DDSP_HIP_EWS;
+  if ((reinterpret_cast<uintptr_t>(packed) & 3) || (reinterpret_cast<uintptr_t>(y) & 3)) return DDSP_HIP_EINVAL;
+  launch_upsample_stage(x, src, y, static_cast<const float*>(packed), B, Cout, Tin, u, s, S(stream));
+  return finish();
+}
+
+int ddsp_hip_output_head_tile(int C) { return gentail::head_shape_ok(C) ? gentail::kHeadTile : 0; }
+
+int ddsp_hip_output_head(const float* x, const float* w, const float* bias, float slope, float* y, int B, int C, long T,
+                         void* stream) {
+  if (B < 0 || T < 1 || !(slope == slope) || slope - slope != 0.f) return DDSP_HIP_EINVAL;
+  if (!gentail::head_shape_ok(C) || T > (1L << 40)) return DDSP_HIP_ESHAPE;
+  if (B == 0) return 0;
+  if (!x || !w || !bias || !y || x == y) return DDSP_HIP_EINVAL;
+  if (reinterpret_cast<uintptr_t>(y) & 3) return DDSP_HIP_EINVAL;
+  launch_output_head(x, w, bias, slope, y, B, C, T, S(stream));
   return finish();
 }
 

@@ -4,6 +4,9 @@ f32 MFMA GEMMs with the intermediate in LDS, and the ``xs / num_kernels`` sum fo
 
   resblock1                  the functional form: ``x [B, C, T]``, one ``(w1, b1, w2, b2)`` per pair, the dilations
   mrf_stage                  ``sum(block_j(x)) / len(blocks)`` of one stage, accumulated and divided in the kernels' epilogue
+  upsample_stage             the seam in front of a stage (csrc/generator_tail.h): ``ConvTranspose1d(lrelu(x)) + noise_conv(source)``
+                             in one launch, the transposed convolution as polyphase f32 MFMA GEMMs
+  output_head                ``tanh(conv_post(lrelu(x)))``, one vector kernel
   patch_reference_generator  rebinds ``ResBlock1.forward`` and ``Generator.forward`` of an importable reference checkout
   unpatch_reference_generator
 
@@ -13,6 +16,12 @@ weight-norm hook recomputes ``weight`` in a forward pre-hook, which a call that 
 Everything else -- 128 / 256 channels, ``ResBlock2``, training, CPU tensors -- takes the reference's own forward unchanged.
 ``TORCH_FASTER`` lists the (C, k) the measurements on one MI355X (tools/resblock_bench.py) found faster as the
 torch op chain: those are routed to it as well.
+
+The seam and the head follow the same rules (``seam_eligible``, ``head_eligible``): Cout in {16, 32, 64} from 2 Cout channels,
+``ConvTranspose1d(2 Cout, Cout, 2 u, u, padding u / 2)`` with u in {2, 4, 8}, the noise conv ``Conv1d(1, Cout, 2 s, s, padding s // 2)``
+with s in {2, 4} or ``Conv1d(1, Cout, 1)``, a source of s u Tin samples; ``Conv1d(C, 1, 7, padding 3)`` for the head.  The 512 -> 256
+and 256 -> 128 seams, weight-normed modules and calls that need a gradient run the torch line.  ``SEAM_TORCH_FASTER`` and
+``HEAD_TORCH_FASTER`` play ``TORCH_FASTER``'s part (tools/generator_tail_bench.py).
 """
 import ctypes
 import threading
@@ -27,12 +36,20 @@ KERNEL_SIZES = (3, 7, 11)
 LRELU_SLOPE = 0.1
 # (C, k) -> the number of columns T below which the same-GPU torch chain was measured faster (None: at every T)
 TORCH_FASTER = {}
+UPSAMPLE_RATES = (2, 4, 8)
+NOISE_STRIDES = (1, 2, 4)
+HEAD_SLOPE = 0.01                                      # F.leaky_relu's default, models.py:260
+HEAD_TAPS = 7
+# (Cout, u) -> the number of input columns Tin below which the torch chain was measured faster (None: at every Tin); C -> T
+SEAM_TORCH_FASTER = {}
+HEAD_TORCH_FASTER = {}
 
 _LOCK = threading.Lock()
 _PACKED = {}                                           # key of the weights -> (versions, device table, the tensors kept alive)
 _PACKED_MAX = 256
 _WS = {}                                               # device -> the hand-over buffer between pairs, grown on demand and kept
-CALLS = {"hip": 0, "reference": 0}                     # dispatch counters (tests and tools read them)
+# dispatch counters (tests and tools read them): "hip" / "reference" count residual blocks, the others seams and heads
+CALLS = {"hip": 0, "reference": 0, "seam_hip": 0, "seam_reference": 0, "head_hip": 0, "head_reference": 0}
 
 
 def tile(C, k):
@@ -137,6 +154,107 @@ def mrf_stage(x, blocks):
     return xs
 
 
+def seam_tile(Cout, u):
+    """input columns per workgroup of the seam (``ddsp_hip_upsample_stage_tile``)"""
+    return int(_ffi.lib().ddsp_hip_upsample_stage_tile(Cout, u))
+
+
+def head_tile(C):
+    """outputs per workgroup of the head (``ddsp_hip_output_head_tile``)"""
+    return int(_ffi.lib().ddsp_hip_output_head_tile(C))
+
+
+def _packed_seam(tensors, Cout, u, s, device):
+    """the seam's weight table on ``device``, cached like ``_packed``'s: by ``data_ptr``, rebuilt on a new ``_version``"""
+    key = (str(device), "seam", Cout, u, s) + tuple(t.data_ptr() for t in tensors)
+    versions = tuple(t._version for t in tensors)
+    hit = _PACKED.get(key)
+    if hit is not None and hit[0] == versions:
+        return hit[1]
+    lib = _ffi.lib()
+    with torch.no_grad():
+        wu, bu, wn, bn = [t.detach().to("cpu", torch.float32).contiguous() for t in tensors]
+    nbytes = int(lib.ddsp_hip_upsample_stage_pack_bytes(Cout, u, s))
+    if nbytes == 0:
+        raise ValueError("upsample_stage: Cout = %d, u = %d, s = %d is outside the kernel's range" % (Cout, u, s))
+    host = torch.empty(nbytes // 4, dtype=torch.float32)
+    _ffi.check(lib.ddsp_hip_upsample_stage_pack(wu.data_ptr(), bu.data_ptr(), wn.data_ptr(), bn.data_ptr(), Cout, u, s,
+                                                host.data_ptr(), nbytes))
+    table = host.to(device)
+    with _LOCK:
+        while len(_PACKED) >= _PACKED_MAX:
+            _PACKED.pop(next(iter(_PACKED)))
+        _PACKED[key] = (versions, table, list(tensors))
+    return table
+
+
+def seam_shape_ok(Cin, Cout, u, s):
+    return Cout in CHANNELS and Cin == 2 * Cout and u in UPSAMPLE_RATES and s in NOISE_STRIDES
+
+
+def upsample_stage(x, up_weight, up_bias, stride, source, noise_weight, noise_bias, noise_stride, out=None):
+    """``ConvTranspose1d(lrelu(x, 0.1)) + noise_conv(source)`` of one stage on the HIP kernel: ``x [B, 2 Cout, Tin]`` float32,
+    ``up_weight [2 Cout, Cout, 2 stride]`` (ConvTranspose1d's order), ``source [B, 1, noise_stride stride Tin]`` (or without the
+    channel axis), ``noise_weight [Cout, 1, 2 noise_stride]`` (``[Cout, 1, 1]`` at ``noise_stride`` 1).  Returns ``[B, Cout,
+    stride Tin]``.  No synchronisation; the only allocation is the result (when ``out`` is None) once the weight table exists."""
+    _ffi.check_device(x, source, out)
+    if x.dtype != torch.float32 or x.dim() != 3 or source.dtype != torch.float32:
+        raise ValueError("upsample_stage: x must be a float32 [B, C, T] tensor and source float32")
+    B, Cin, Tin = x.shape
+    u, s = int(stride), int(noise_stride)
+    Cout = up_weight.shape[1] if up_weight.dim() == 3 else -1
+    if not seam_shape_ok(Cin, Cout, u, s):
+        raise ValueError("upsample_stage: %d -> %d channels, stride %d, noise stride %d is outside the kernel's range"
+                         % (Cin, Cout, u, s))
+    ks = 2 * s if s > 1 else 1
+    if (tuple(up_weight.shape) != (Cin, Cout, 2 * u) or tuple(up_bias.shape) != (Cout,)
+            or tuple(noise_weight.shape) != (Cout, 1, ks) or tuple(noise_bias.shape) != (Cout,)):
+        raise ValueError("upsample_stage: weights must be [2 Cout, Cout, 2 u], [Cout], [Cout, 1, 2 s or 1], [Cout]")
+    if Tin < 1:
+        raise ValueError("upsample_stage: Tin must be positive")
+    Tout = u * Tin
+    if source.shape[0] != B or source.numel() != B * s * Tout or source.shape[-1] != s * Tout:
+        raise ValueError("upsample_stage: source must hold %d samples per utterance" % (s * Tout))
+    x, source = x.contiguous(), source.contiguous()
+    y = torch.empty((B, Cout, Tout), dtype=torch.float32, device=x.device) if out is None else out
+    if not y.is_contiguous() or tuple(y.shape) != (B, Cout, Tout) or y.dtype != torch.float32:
+        raise ValueError("upsample_stage: out must be a contiguous float32 [B, Cout, u Tin] tensor")
+    if B == 0:
+        return y
+    table = _packed_seam((up_weight, up_bias, noise_weight, noise_bias), Cout, u, s, x.device)
+    CALLS["seam_hip"] += 1
+    _ffi.check(_ffi.lib().ddsp_hip_upsample_stage(x.data_ptr(), source.data_ptr(), y.data_ptr(), table.data_ptr(),
+                                                  table.numel() * 4, B, Cout, Tin, u, s, _ffi.stream_of(x)))
+    return y
+
+
+def output_head(x, weight, bias, slope=HEAD_SLOPE, out=None):
+    """``tanh(conv1d(lrelu(x, slope), weight, bias, padding=3))`` on the HIP kernel: ``x [B, C, T]`` float32, ``weight [1, C, 7]``
+    and ``bias [1]`` float32 on x's device -- the kernel reads them where they are, so there is no table to pack or cache.
+    Returns ``[B, 1, T]``.  No synchronisation, no allocation but the result."""
+    _ffi.check_device(x, weight, bias, out)
+    if x.dtype != torch.float32 or x.dim() != 3:
+        raise ValueError("output_head: x must be a float32 [B, C, T] tensor")
+    B, C, T = x.shape
+    if C not in CHANNELS:
+        raise ValueError("output_head: C = %d is outside the kernel's range" % C)
+    if (tuple(weight.shape) != (1, C, HEAD_TAPS) or tuple(bias.shape) != (1,) or weight.dtype != torch.float32
+            or bias.dtype != torch.float32 or weight.device != x.device or bias.device != x.device):
+        raise ValueError("output_head: weight must be float32 [1, C, 7] and bias [1] on x's device")
+    if T < 1:
+        raise ValueError("output_head: T must be positive")
+    x, weight = x.contiguous(), weight.detach().contiguous()
+    y = torch.empty((B, 1, T), dtype=torch.float32, device=x.device) if out is None else out
+    if not y.is_contiguous() or tuple(y.shape) != (B, 1, T) or y.dtype != torch.float32:
+        raise ValueError("output_head: out must be a contiguous float32 [B, 1, T] tensor")
+    if B == 0:
+        return y
+    CALLS["head_hip"] += 1
+    _ffi.check(_ffi.lib().ddsp_hip_output_head(x.data_ptr(), weight.data_ptr(), bias.detach().data_ptr(), float(slope),
+                                               y.data_ptr(), B, C, T, _ffi.stream_of(x)))
+    return y
+
+
 # ---- the reference's modules --------------------------------------------------------------------------------------------------
 
 def _plain_conv(c, C, k, d):
@@ -225,9 +343,100 @@ def stage_forward(blocks, x):
     return xs / len(blocks)
 
 
+def _plain_module(c, cls):
+    """a module of class ``cls`` whose ``weight`` is a plain float32 parameter, with a bias, zero padding, one group, no dilation
+    and no hook (a weight-norm hook recomputes ``weight``; any other expects the module's own forward to run)"""
+    if not isinstance(c, cls) or not isinstance(c._parameters.get("weight"), torch.Tensor):
+        return False
+    if c._forward_pre_hooks or c._forward_hooks:
+        return False
+    return (c.groups == 1 and c.dilation == (1,) and c.padding_mode == "zeros" and c.bias is not None
+            and c.weight.dtype == torch.float32 and c.bias.dtype == torch.float32)
+
+
+def _pad_of(c):
+    return tuple(c.padding) if isinstance(c.padding, (tuple, list)) else (c.padding,)
+
+
+def _seam_spec(up, noise_conv):
+    """``(Cout, u, s)`` of an upsampling the kernel can stand in for, or None"""
+    if not _plain_module(up, torch.nn.ConvTranspose1d) or not _plain_module(noise_conv, torch.nn.Conv1d):
+        return None
+    Cout, u = up.out_channels, up.stride[0]
+    if (up.in_channels != 2 * Cout or up.kernel_size != (2 * u,) or _pad_of(up) != (u // 2,)
+            or tuple(up.output_padding) != (0,)):
+        return None
+    s = noise_conv.stride[0]
+    if noise_conv.in_channels != 1 or noise_conv.out_channels != Cout:
+        return None
+    if noise_conv.kernel_size == (1,):
+        if s != 1 or _pad_of(noise_conv) != (0,):
+            return None
+    elif s < 2 or noise_conv.kernel_size != (2 * s,) or _pad_of(noise_conv) != (s // 2,):
+        return None
+    if not seam_shape_ok(2 * Cout, Cout, u, s):
+        return None
+    return Cout, u, s
+
+
+def _needs_grad(tensors):
+    return torch.is_grad_enabled() and any(t.requires_grad for t in tensors)
+
+
+def seam_eligible(up, noise_conv, x, source):
+    """``(Cout, u, s)`` to run ``up(lrelu(x)) + noise_conv(source)`` with the HIP kernel, or None: the torch line"""
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() != 3 or x.shape[-1] < 1 or not _on_device(x):
+        return None
+    if not isinstance(source, torch.Tensor) or source.dtype != torch.float32 or source.dim() != 3 or source.device != x.device:
+        return None
+    spec = _seam_spec(up, noise_conv)
+    if spec is None or x.shape[1] != 2 * spec[0]:
+        return None
+    Cout, u, s = spec
+    if tuple(source.shape) != (x.shape[0], 1, s * u * x.shape[-1]):
+        return None
+    if _needs_grad([x, source, up.weight, up.bias, noise_conv.weight, noise_conv.bias]):
+        return None
+    if (Cout, u) in SEAM_TORCH_FASTER and (SEAM_TORCH_FASTER[(Cout, u)] is None or x.shape[-1] < SEAM_TORCH_FASTER[(Cout, u)]):
+        return None
+    return spec
+
+
+def seam_forward(up, noise_conv, x, source):
+    """one stage's ``up(lrelu(x)) + noise_conv(source)``: the HIP kernel when eligible, the reference's line otherwise"""
+    spec = seam_eligible(up, noise_conv, x, source)
+    if spec is None:
+        CALLS["seam_reference"] += 1
+        return up(F.leaky_relu(x, LRELU_SLOPE)) + noise_conv(source)
+    return upsample_stage(x, up.weight, up.bias, spec[1], source, noise_conv.weight, noise_conv.bias, spec[2])
+
+
+def head_eligible(conv_post, x):
+    """True to run ``tanh(conv_post(lrelu(x)))`` with the HIP kernel"""
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() != 3 or x.shape[-1] < 1 or not _on_device(x):
+        return False
+    if not _plain_module(conv_post, torch.nn.Conv1d):
+        return False
+    C = conv_post.in_channels
+    if (C not in CHANNELS or x.shape[1] != C or conv_post.out_channels != 1 or conv_post.kernel_size != (HEAD_TAPS,)
+            or conv_post.stride != (1,) or _pad_of(conv_post) != (3,) or conv_post.weight.device != x.device):
+        return False
+    if _needs_grad([x, conv_post.weight, conv_post.bias]):
+        return False
+    return not (C in HEAD_TORCH_FASTER and (HEAD_TORCH_FASTER[C] is None or x.shape[-1] < HEAD_TORCH_FASTER[C]))
+
+
+def head_forward(conv_post, x):
+    """``tanh(conv_post(lrelu(x)))``: the HIP kernel when eligible, the reference's line otherwise"""
+    if not head_eligible(conv_post, x):
+        CALLS["head_reference"] += 1
+        return torch.tanh(conv_post(F.leaky_relu(x)))
+    return output_head(x, conv_post.weight, conv_post.bias, HEAD_SLOPE)
+
+
 def patch_reference_generator():
-    """Route ``nsf_hifigan.models.ResBlock1.forward`` and the per-stage block sum of ``Generator.forward`` of an importable
-    reference checkout through the dispatchers above.  Idempotent; returns the module."""
+    """Route ``nsf_hifigan.models.ResBlock1.forward`` and, in ``Generator.forward`` of an importable reference checkout, each
+    stage's upsampling seam, its block sum and the output head through the dispatchers above.  Idempotent; returns the module."""
     import nsf_hifigan.models as nm
     if hasattr(nm.ResBlock1, "_reference_forward"):
         return nm
@@ -244,9 +453,9 @@ def patch_reference_generator():
         x = self.conv_pre(x)
         n = self.num_kernels
         for i, (up, noise_conv) in enumerate(zip(self.ups, self.noise_convs)):
-            x = up(F.leaky_relu(x, nm.LRELU_SLOPE)) + noise_conv(source)
+            x = seam_forward(up, noise_conv, x, source)
             x = stage_forward(self.resblocks[i * n:(i + 1) * n], x)
-        return torch.tanh(self.conv_post(F.leaky_relu(x)))
+        return head_forward(self.conv_post, x)
 
     nm.ResBlock1.forward = resblock_forward
     nm.Generator.forward = generator_forward

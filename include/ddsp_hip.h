@@ -13,8 +13,8 @@
  *   - tensors are float32 row-major; B = utterances, F = frames, hop = samples per frame,
  *     T = F*hop; control tensors take a row stride `ld` (floats between consecutive frames) so
  *     the torch.split views of Unit2Control's output can be passed without a copy;
- *   - more than 65 535 utterances in one call (a grid's limit in y and z): ddsp_hip_resblock1, ddsp_hip_resample and
- *     ddsp_hip_mel_shifted_spectrogram split the batch into launches of 65 535; ddsp_hip_fast_source and
+ *   - more than 65 535 utterances in one call (a grid's limit in y and z): ddsp_hip_resblock1, ddsp_hip_upsample_stage,
+ *     ddsp_hip_output_head, ddsp_hip_resample and ddsp_hip_mel_shifted_spectrogram split the batch into launches of 65 535; ddsp_hip_fast_source and
  *     ddsp_hip_combsubsuperfast_synth run their exciter on a flat grid then; ddsp_hip_sine_source(_drawn),
  *     ddsp_hip_spectral_loss(_backward), ddsp_hip_stft_loss(_backward), ddsp_hip_mel_spectrogram_backward,
  *     ddsp_hip_sola_splice, ddsp_hip_volume, ddsp_hip_gate, ddsp_hip_pool1d, ddsp_hip_fft_convolve with
@@ -549,6 +549,37 @@ size_t ddsp_hip_resblock1_workspace_bytes(int B, int C, long T, int pairs);
 int ddsp_hip_resblock1(const float* x, float* y, const void* packed, size_t packed_bytes, int B, int C, long T, int k,
                        const int* dilations, int pairs, const float* acc_in, float scale, void* ws, size_t ws_bytes,
                        void* stream);
+
+/* The rest of the NSF-HiFiGAN generator between the 128-channel stage and the waveform (nsf_hifigan/models.py:249-252, :260-262),
+ * csrc/generator_tail.h.  As above, these entry points came after version 165 without a version step.
+ *
+ * The upsampling seam of a stage:
+ *   y[b, co, t] = bu[co] + sum over (ci, j) of lrelu_0.1(x)[b, ci, q] Wu[ci, co, j] over t = u q - u / 2 + j   (ConvTranspose1d(2 Cout,
+ *                 Cout, 2 u, u, padding u / 2))  + bn[co] + sum over m of src[b, t s - s / 2 + m] Wn[co, 0, m]   (Conv1d(1, Cout, 2 s,
+ *                 s, padding s / 2), or Conv1d(1, Cout, 1) at s = 1), zeros outside both inputs.
+ * Cout in {16, 32, 64}, u in {2, 4, 8}, s in {1, 2, 4} (DDSP_HIP_ESHAPE otherwise); x [B, 2 Cout, Tin], src [B, s u Tin],
+ * y [B, Cout, u Tin], all contiguous; 1 <= Tin <= 2^30.
+ * ddsp_hip_upsample_stage_tile: input columns per workgroup (128, or 64 at Cout = 64, u = 8); 0 for a (Cout, u) outside the range.
+ * ddsp_hip_upsample_stage_pack_bytes / _pack: HOST weights wu [2 Cout][Cout][2 u] (ConvTranspose1d's order: input channel
+ * first), bu [Cout], wn [Cout][1][2 s] ([Cout][1][1] at s = 1), bn [Cout] -> the table the kernel reads, written to HOST memory
+ * (the caller copies it to the device once and keeps it).  0 bytes / DDSP_HIP_ESHAPE out of range, DDSP_HIP_EWS short.
+ * ddsp_hip_upsample_stage: one launch (per 65 535 utterances), the transposed convolution as u polyphase f32 MFMA GEMMs, the
+ * noise convolution and the add in the same launch.  y must be neither x nor src.  B = 0 is a no-op.
+ *
+ * The output head: y[b, 0, t] = tanh(bias + sum over (ci, j < 7) of lrelu_slope(x)[b, ci, t + j - 3] w[0, ci, j]), zeros outside
+ * [0, T); C in {16, 32, 64} (DDSP_HIP_ESHAPE otherwise), x [B, C, T], y [B, 1, T], w [1][C][7] and bias [1] DEVICE memory (the
+ * Conv1d's own parameters), slope finite (the reference's F.leaky_relu default is 0.01).  ddsp_hip_output_head_tile: outputs
+ * per workgroup (1024), 0 for another C.  One launch (per 65 535 utterances); x must not be y; B = 0 is a no-op.
+ * Neither allocates nor synchronises. */
+int ddsp_hip_upsample_stage_tile(int Cout, int u);
+size_t ddsp_hip_upsample_stage_pack_bytes(int Cout, int u, int s);
+int ddsp_hip_upsample_stage_pack(const float* wu, const float* bu, const float* wn, const float* bn, int Cout, int u, int s,
+                                 void* packed, size_t packed_bytes);
+int ddsp_hip_upsample_stage(const float* x, const float* src, float* y, const void* packed, size_t packed_bytes, int B, int Cout,
+                            long Tin, int u, int s, void* stream);
+int ddsp_hip_output_head_tile(int C);
+int ddsp_hip_output_head(const float* x, const float* w, const float* bias, float slope, float* y, int B, int C, long T,
+                         void* stream);
 
 #ifdef __cplusplus
 }
