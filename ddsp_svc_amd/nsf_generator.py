@@ -7,6 +7,7 @@ f32 MFMA GEMMs with the intermediate in LDS, and the ``xs / num_kernels`` sum fo
   upsample_stage             the seam in front of a stage (csrc/generator_tail.h): ``ConvTranspose1d(lrelu(x)) + noise_conv(source)``
                              in one launch, the transposed convolution as polyphase f32 MFMA GEMMs
   output_head                ``tanh(conv_post(lrelu(x)))``, one vector kernel
+  generator_forward          ``Generator.forward`` of any module with the reference generator's attributes, stage by stage
   patch_reference_generator  rebinds ``ResBlock1.forward`` and ``Generator.forward`` of an importable reference checkout
   unpatch_reference_generator
 
@@ -23,6 +24,7 @@ with s in {2, 4} or ``Conv1d(1, Cout, 1)``, a source of s u Tin samples; ``Conv1
 and 256 -> 128 seams, weight-normed modules and calls that need a gradient run the torch line.  ``SEAM_TORCH_FASTER`` and
 ``HEAD_TORCH_FASTER`` play ``TORCH_FASTER``'s part (tools/generator_tail_bench.py).
 """
+import collections
 import ctypes
 import threading
 
@@ -47,7 +49,9 @@ HEAD_TORCH_FASTER = {}
 _LOCK = threading.Lock()
 _PACKED = {}                                           # key of the weights -> (versions, device table, the tensors kept alive)
 _PACKED_MAX = 256
-_WS = {}                                               # device -> the hand-over buffer between pairs, grown on demand and kept
+# (device, raw handle of the caller's stream) -> the hand-over buffer between pairs, grown on demand and kept; LRU, as _ffi._AUX
+_WS = collections.OrderedDict()
+_WS_MAX = 16
 # dispatch counters (tests and tools read them): "hip" / "reference" count residual blocks, the others seams and heads
 CALLS = {"hip": 0, "reference": 0, "seam_hip": 0, "seam_reference": 0, "head_hip": 0, "head_reference": 0}
 
@@ -88,16 +92,31 @@ def _packed(weights, C, k, device):
     return table
 
 
-def _workspace(nbytes, device):
-    ws = _WS.get(device)
-    if ws is None or ws.numel() * 4 < nbytes:
-        ws = _WS[device] = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=device)
+def _workspace(nbytes, x):
+    """the hand-over buffer of ``x``'s device AND the caller's stream there: the launches of one call write and read it on that
+    stream, so two streams must never see the same one.  A buffer is allocated while its stream is the current one, so the
+    caching allocator hands its memory on only to later work of that same stream: a buffer that growth, the LRU bound or
+    ``release_workspace`` drops while launches still use it is reused behind them, never beside them.  During a graph
+    capture the cache is neither read nor grown: the buffer comes from the graph's own pool and belongs to the graph, which
+    therefore holds no address that a later growth or ``release_workspace`` frees."""
+    n = (nbytes + 3) // 4
+    if x.is_cuda and torch.cuda.is_current_stream_capturing():
+        return torch.empty(n, dtype=torch.float32, device=x.device)
+    key = (str(x.device), _ffi.stream_of(x))
+    with _LOCK:
+        ws = _WS.get(key)
+        if ws is None or ws.numel() < n:
+            ws = _WS[key] = torch.empty(n, dtype=torch.float32, device=x.device)
+            while len(_WS) > _WS_MAX:
+                _WS.popitem(last=False)
+        _WS.move_to_end(key)
     return ws
 
 
 def release_workspace():
-    """drop the cached hand-over buffers (2 [B, C, T] activations per device at the largest shape seen)"""
-    _WS.clear()
+    """drop the cached hand-over buffers of every device and stream (2 [B, C, T] activations each at the largest shape seen)"""
+    with _LOCK:
+        _WS.clear()
 
 
 def shape_ok(C, k, dilations):
@@ -136,12 +155,12 @@ def resblock1(x, weights, dilations, acc=None, scale=None, out=None):
     table = _packed(weights, C, k, x.device)
     pairs = len(dilations)
     nws = int(lib.ddsp_hip_resblock1_workspace_bytes(B, C, T, pairs))
-    ws = _workspace(nws, x.device) if nws else None
+    ws = _workspace(nws, x) if nws else None          # its real size goes to the library, which refuses one too small
     dil = (ctypes.c_int * pairs)(*[int(d) for d in dilations])
     CALLS["hip"] += 1
     _ffi.check(lib.ddsp_hip_resblock1(x.data_ptr(), y.data_ptr(), table.data_ptr(), table.numel() * 4, B, C, T, k,
                                       ctypes.addressof(dil), pairs, _ffi.ptr(acc), 0.0 if scale is None else float(scale),
-                                      _ffi.ptr(ws), nws, _ffi.stream_of(x)))
+                                      _ffi.ptr(ws), 0 if ws is None else ws.numel() * 4, _ffi.stream_of(x)))
     return y
 
 
@@ -434,6 +453,33 @@ def head_forward(conv_post, x):
     return output_head(x, conv_post.weight, conv_post.bias, HEAD_SLOPE)
 
 
+_GENERATOR_ATTRS = ("conv_pre", "ups", "noise_convs", "resblocks", "num_kernels", "conv_post", "m_source", "upp")
+
+
+def generator_forward(gen, x, f0, fallback=None):
+    """``Generator.forward(x, f0)`` of a module with the reference generator's attributes (``conv_pre``, ``ups``,
+    ``noise_convs``, ``resblocks``, ``num_kernels``, ``conv_post``, ``m_source``, ``upp``): the source and ``conv_pre`` as torch
+    runs them, then every stage's seam and block sum and the head through the dispatchers above, each of which decides for
+    itself.  The whole call goes to ``fallback(gen, x, f0)`` (None: ``type(gen).forward``) when the first block does not even
+    name a ``convs1`` / ``convs2`` pair (ResBlock2), ``x`` is not a float32 tensor on the GPU, or a gradient is needed."""
+    if fallback is None:
+        fallback = type(gen).forward
+    if any(not hasattr(gen, a) for a in _GENERATOR_ATTRS):
+        return fallback(gen, x, f0)
+    first = gen.resblocks[0] if len(gen.resblocks) else None
+    if (getattr(first, "convs1", None) is None or getattr(first, "convs2", None) is None or not isinstance(x, torch.Tensor)
+            or x.dtype != torch.float32 or not _on_device(x)
+            or (torch.is_grad_enabled() and any(p.requires_grad for p in gen.parameters()))):
+        return fallback(gen, x, f0)
+    source = gen.m_source(f0, gen.upp).transpose(1, 2)
+    x = gen.conv_pre(x)
+    n = gen.num_kernels
+    for i, (up, noise_conv) in enumerate(zip(gen.ups, gen.noise_convs)):
+        x = seam_forward(up, noise_conv, x, source)
+        x = stage_forward(gen.resblocks[i * n:(i + 1) * n], x)
+    return head_forward(gen.conv_post, x)
+
+
 def patch_reference_generator():
     """Route ``nsf_hifigan.models.ResBlock1.forward`` and, in ``Generator.forward`` of an importable reference checkout, each
     stage's upsampling seam, its block sum and the output head through the dispatchers above.  Idempotent; returns the module."""
@@ -444,21 +490,11 @@ def patch_reference_generator():
     nm.Generator._reference_forward = nm.Generator.forward
     ref_generator_forward = nm.Generator.forward
 
-    def generator_forward(self, x, f0):
-        first = self.resblocks[0] if len(self.resblocks) else None
-        if (not isinstance(first, nm.ResBlock1) or not isinstance(x, torch.Tensor) or x.dtype != torch.float32
-                or not _on_device(x) or (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()))):
-            return ref_generator_forward(self, x, f0)
-        source = self.m_source(f0, self.upp).transpose(1, 2)
-        x = self.conv_pre(x)
-        n = self.num_kernels
-        for i, (up, noise_conv) in enumerate(zip(self.ups, self.noise_convs)):
-            x = seam_forward(up, noise_conv, x, source)
-            x = stage_forward(self.resblocks[i * n:(i + 1) * n], x)
-        return head_forward(self.conv_post, x)
+    def patched_forward(self, x, f0):
+        return generator_forward(self, x, f0, fallback=ref_generator_forward)
 
     nm.ResBlock1.forward = resblock_forward
-    nm.Generator.forward = generator_forward
+    nm.Generator.forward = patched_forward
     return nm
 
 
