@@ -12,8 +12,14 @@
 // Table (built on the host from the float32 bank, resample_table_*, then copied to the device once):
 //   Hdr, then a TileHdr per tile of kTN virtual phases, then the taps of each tile as [kt][kTN] floats (16-byte aligned).
 //   A tile's K range [klo, klo + kt) is the union of its phases' live bands (the taps that are not exactly 0.0f), kt rounded
-//   up to kKC with zero taps.  Taps outside that range are exactly zero, so dropping them changes only the summation order
-//   (for finite input).
+//   up to kKC with zero taps (the kernel reads no sample against those: TileHdr::kl is the length before rounding).
+//   For finite input the trimming changes only the summation order: the taps outside the range are exactly zero.  For a
+//   sample that is inf or NaN it changes which outputs are non-finite, in both directions.  A zero tap that was dropped
+//   no longer turns the output into NaN (0 * inf), while a tile's band is the union over its 32 virtual phases, so a zero
+//   tap inside it that torchaudio's conv1d never multiplies (the shifted copies of the virtual phases add such taps,
+//   h'[g n + j, k'] outside k' - g o in [0, K)) now does.  What holds: an output with a non-zero tap on the sample is
+//   non-finite; no output outside the virtual rows q' whose window [q' G o, q' G o + (G - 1) o + K) of the padded input
+//   covers the sample is; and every finite output has the bits it has with that sample set to zero.
 //
 // k_resample: grid (ceil(M' / kTM), tiles, B), 4 waves.  One workgroup: kTM output rows x one tile of kTN phases.  Stage s
 // holds kKG = 4 kKC taps: the A rows (kTM x kKG, read with bounds checks in place of the zero padding) and the tile's taps
@@ -46,7 +52,7 @@ constexpr int kMagic = 0x52534d50;
 constexpr size_t kTapAlign = 256;
 
 struct Hdr { int magic, o, n, K, G, tiles, pad0, pad1; };   // the kernel checks magic, o, n, K and tiles against its call
-struct TileHdr { int klo, kt, off, pad; };             // off: floats from the start of the tap section
+struct TileHdr { int klo, kt, off, kl; };              // off: floats from the start of the tap section; kl: the band before rounding
 
 inline int virt_group(int n) { return n < kTN ? kTN / n : 1; }
 inline int tiles_of(int n) { return (n * virt_group(n) + kTN - 1) / kTN; }
@@ -113,7 +119,7 @@ __global__ __launch_bounds__(kThreads) void k_resample(Args a) {
         const int e = tid + r * kThreads;
         const int i = e / kKG, k = e % kKG;
         const long p = p0 + (long)i * a.op + k0 + k;
-        ra[r] = (k0 + k < th.kt && p >= 0 && p < a.L) ? xb[p * a.sx] : 0.f;
+        ra[r] = (k0 + k < th.kl && p >= 0 && p < a.L) ? xb[p * a.sx] : 0.f;   // kl, not kt: no sample meets a rounding tap
       }
 #pragma unroll
       for (int r = 0; r < kBLoads; ++r) {
@@ -188,7 +194,7 @@ static inline long resample_layout(const float* bank, int o, int n, int K, resam
     }
     const long kt = any ? ((long)(hi - lo) + kKC - 1) / kKC * kKC : 0;
     if (kt > kMaxBand) return -1;
-    if (th) { th[t].klo = lo; th[t].kt = (int)kt; th[t].off = (int)total; th[t].pad = 0; }
+    if (th) { th[t].klo = lo; th[t].kt = (int)kt; th[t].off = (int)total; th[t].kl = any ? hi - lo : 0; }
     total += kt * kTN;
   }
   return total;
