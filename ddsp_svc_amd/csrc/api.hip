@@ -27,17 +27,12 @@ const char* const kKnobNames[KNOB_COUNT] = {"BLK_WPS", "BLK_RUN", "BLK_PADLDS", 
                                             "AP_BWD_SPLIT", "SINS_SEQ", "BATCH_SPLIT"};
 std::atomic<long> g_knobs[KNOB_COUNT];
 std::once_flag g_knobs_once;
-// A knob whose kernel generation is not compiled into this build (the product library ships ONE generation per kernel; the
-// superseded ones exist only under -DDDSP_AB_GENERATIONS, tools/build_variant.sh) does nothing: setting it is an ERROR from
-// ddsp_hip_set_tuning and a warning from the environment, so that an A/B run cannot measure the same kernel twice under two names.
+// A RETIRED knob chose a kernel generation that the library no longer has (it ships ONE generation per kernel; git keeps the
+// superseded ones, tools/build_prev.sh builds an older commit for an A/B): setting it is an ERROR from ddsp_hip_set_tuning and a
+// warning from the environment, so that a stale A/B script cannot measure the same kernel twice under two names.
 bool knob_is_inert(int i, long v) {
-#ifdef DDSP_AB_GENERATIONS
-  (void)i; (void)v;
-  return false;
-#else
   if (v == 0) return false;
   return i == KNOB_BLK_WPS || i == KNOB_BLK_PADLDS || (i == KNOB_SINS_V1 && v == 2);
-#endif
 }
 void knobs_from_env() {
   for (int i = 0; i < KNOB_COUNT; ++i) {
@@ -46,7 +41,7 @@ void knobs_from_env() {
     const char* e = getenv(name);
     long v = e ? atol(e) : 0;
     if (knob_is_inert(i, v)) {
-      fprintf(stderr, "libddsp_hip: %s=%ld ignored: that kernel generation is not in this build (-DDDSP_AB_GENERATIONS)\n", name, v);
+      fprintf(stderr, "libddsp_hip: %s=%ld ignored: the knob is retired, that kernel generation is no longer in the library\n", name, v);
       v = 0;
     }
     g_knobs[i].store(v, std::memory_order_relaxed);
@@ -319,15 +314,12 @@ bool fused_off() {
 
 // does a CombSub / Sins call of this shape take the fused one-stream layout (combsub_rows / sins_rows)?  One predicate for the
 // launch path and for ddsp_hip_tail_layout, which tells a training caller where the call left its intermediates.
-bool fused_shape_ok(long R, int F, int hop, int n0, int n1, int n2, int fir_impl, bool gen_on, bool combsub) {
+bool fused_shape_ok(long R, int F, int hop, int n0, int n1, int n2, int fir_impl, bool combsub) {
   if (!(R < kSmallRows || !fused_off()) || hop != 512 || t_taps_gemm || knob(KNOB_SMALL_PATH) == 1) return false;
   if (combsub) {
-    (void)gen_on;                                            // (the in-kernel noise draw rides in the paired filter launch as its second job)
+    // (an in-kernel noise draw changes nothing here: it rides in the paired filter launch as its second job)
     if (n0 != 256 || n1 != 256 || n2 != 256 || !(fir_impl == 0 || fir_impl == 5)) return false;
     if ((long)F * hop > (1L << 24) || R >= (1L << 31) - 64) return false;       // the exciter job's shift form (make_exciter_job)
-#ifdef DDSP_AB_GENERATIONS                                   // (the two-wave kernel of the A/B builds takes no second job: launch_fir_blk's predicate)
-    if (!((knob(KNOB_BLK_WPS) == 0 || knob(KNOB_BLK_WPS) >= 3) && knob(KNOB_BLK_PADLDS) == 0)) return false;
-#endif
     return true;
   }
   return n1 == 256 && n2 == 256;                              // Sins: all-pass and noise filter at 256 bins (n0 = harmonics)
@@ -339,12 +331,7 @@ bool fused_shape_ok(long R, int F, int hop, int n0, int n1, int n2, int fir_impl
 // phase too, but its dynamic window clamps the upper side only, core.py:245: not even.)  Knob TAPS_FULL = 1: whole rows (same-box
 // A/Bs; same bits either way: the whole rows hold the same numbers twice).  No backward kernel reads these taps.
 bool taps_half_ok(int F, int hop, int fir_impl) {
-#if defined(DDSP_AB_GENERATIONS) || defined(DDSP_PFA_NOSYM)
-  (void)F; (void)hop; (void)fir_impl;
-  return false;
-#else
   return knob(KNOB_TAPS_FULL) != 1 && hop == 512 && (fir_impl == 0 || fir_impl == 5) && (long)F * hop < (1L << 28);
-#endif
 }
 
 size_t carve_synth(Carver& c, int B, int F, int hop, int n_max, SynthWs& w) {
@@ -687,7 +674,7 @@ int sins_rows(const TailCall& a, SynthWs& w, hipStream_t st, void* aux_stream) {
   // The fused layout (as combsub_rows below; round 6: at every shape): both tap syntheses in one launch -- four dependent
   // launches on the caller's stream: sinusoid bank | taps (grid.y) | noise filter | all-pass filter + noise.  Same kernels, same
   // arguments, same bits as the two-stream layout below.  [MI355X] B = 32 x 10 s, same box: 0.3367 -> 0.3212 ms (r06_v10s_*).
-  if (fused_shape_ok(R, F, hop, H, n_ap, n_nz, a.fir_impl, a.gen.on != 0, false)) {
+  if (fused_shape_ok(R, F, hop, H, n_ap, n_nz, a.fir_impl, false)) {
     const int r = launch_sins_bank(a.f0_frames, a.initial_phase, a.c0, a.ld0, B, F, hop, H, a.sr, a.infer, a.phase0, w.buf0, st);
     if (r == -1) return DDSP_HIP_EHOP;
     if (r == -2) return DDSP_HIP_ESHAPE;
@@ -757,7 +744,7 @@ int combsub_rows(const TailCall& a, SynthWs& w, hipStream_t st, void* aux_stream
   // the hardware-queue question of round 5 are gone from this path.
   // Same kernels, same arguments as the layouts below (same bits below 4096 frames: tests/test_small_shapes.py; above, the paired
   // filters' run split differs: rounding-level); knob SMALL_PATH = 1: never; knob STREAM_LAYOUT = 1 / 4: not at batch shapes.
-  if (w.taps3 && fused_shape_ok(R, F, hop, n_ap, n_harm, n_nz, a.fir_impl, a.gen.on != 0, true)) {
+  if (w.taps3 && fused_shape_ok(R, F, hop, n_ap, n_harm, n_nz, a.fir_impl, true)) {
     ExciterJob exc;
     if (make_exciter_job(a.f0_frames, a.initial_phase, B, F, hop, a.sr, a.infer, a.phase0, w.buf0, &exc) != 0) return DDSP_HIP_EHOP;
     TapsJobs jobs;
@@ -838,12 +825,13 @@ size_t ddsp_hip_synth_workspace_bytes(int B, int F, int hop, int n_max) {
 int ddsp_hip_tail_layout(int combsub, int B, int F, int hop, int n0, int n1, int n2, int fir_impl, int in_kernel_noise,
                          long long offsets[6]) {
   if (!offsets || B <= 0 || F <= 0 || hop <= 0) return DDSP_HIP_EINVAL;
+  (void)in_kernel_noise;                                       // (kept in the signature; no layout depends on it)
   for (int i = 0; i < 6; ++i) offsets[i] = -1;
   const TapsFormScope form;
   int n_max = n1 > n2 ? n1 : n2;
   if (combsub && n0 > n_max) n_max = n0;
   if (lane_plan(B, F).nsub > 1) return 0;                      // sub-batches on lanes: slots are re-used, nothing survives the call
-  if (!fused_shape_ok((long)B * F, F, hop, n0, n1, n2, fir_impl, in_kernel_noise != 0, combsub != 0)) return 0;
+  if (!fused_shape_ok((long)B * F, F, hop, n0, n1, n2, fir_impl, combsub != 0)) return 0;
   constexpr uintptr_t kBase = 4096;                            // a carve over a pretend base: offsets = pointers - base, null = absent
   Carver c(reinterpret_cast<void*>(kBase), (size_t)1 << 60);
   SynthWs w;

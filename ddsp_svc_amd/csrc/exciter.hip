@@ -153,122 +153,19 @@ __device__ __forceinline__ f32x2 lerp_pair(f32x2 lam, f32x2 ad) {
 #endif
 }
 
-#ifdef DDSP_AB_GENERATIONS                       // round 1 / 2's 16-harmonic blocks: A/B builds only (tools/build_variant.sh)
-__global__ void __launch_bounds__(256) k_sins_bank2(const float* __restrict__ f0_frames,
-                                                    const float* __restrict__ initial_phase,
-                                                    const float* __restrict__ c_amp, long ld_amp, int F, int H,
-                                                    Upsampler up, PhaseCfg cfg, const double* __restrict__ phase0,
-                                                    float* __restrict__ out) {
-  constexpr int HOP = 512;
-  HIP_DYNAMIC_SHARED(float, amp)                    // [HP][2]: (A[f][k], A[f+1][k]) for k < H, zero up to HP
-  __shared__ double wsum[4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const long fr = blockIdx.x;
-  const long b = fr / F;
-  const int f = (int)(fr - b * F);
-  const int HP = (H + 15) & ~15;
-  const float* f0_row = f0_frames + b * F;
-  const float nyq = cfg.sr_f / 2.0f;
-  const int f1 = f + 1 < F ? f + 1 : F - 1;           // last frame held (core.py:68)
-  for (int k = tid; k < HP; k += 256) {
-    float a0 = 0.f, a1 = 0.f;
-    if (k < H) {
-      const float e0 = expf(c_amp[(b * F + f) * ld_amp + k]) / 128.0f;       // vocoder.py:580
-      const float e1 = expf(c_amp[(b * F + f1) * ld_amp + k]) / 128.0f;
-      const float kk = (float)(k + 1);
-      a0 = e0 * ((f0_row[f] * kk < nyq ? 1.0f : 0.0f) + 1e-7f);             // core.py:75-76
-      a1 = e1 * ((f0_row[f1] * kk < nyq ? 1.0f : 0.0f) + 1e-7f);
-    }
-    amp[2 * k] = a0;
-    amp[2 * k + 1] = a1 - a0;                       // the frame-to-frame step: upsample(A)[t] = A[f] + lambda (A[f+1] - A[f])
-  }
-  // wrapped phase of this thread's two samples (vocoder.py:564-572): float64 terms, block-wide exclusive scan
-  const Upsampler::Row3 rows = up.load3(f0_row, f);
-  const float ip = cfg.has_ip ? initial_phase[b] : 0.0f;
-  const long t0 = (long)f * HOP + 2 * tid;
-  const double q0 = cfg.term(up.at3_pow2(rows, 2 * tid));       // the launcher has checked up.shift > 0 (hop 512, F hop <= 2^24)
-  const double q1 = cfg.term(up.at3_pow2(rows, 2 * tid + 1));
-  const double mine = q0 + q1;
-  const double excl = wave_excl_scan(mine, lane);
-  if (lane == 63) wsum[wave] = excl + mine;
-  __syncthreads();                                  // also publishes amp[]
-  double base = phase0[fr] + excl;
-  for (int w = 0; w < wave; ++w) base += wsum[w];
-  const float xa = cfg.wrap(base + q0, ip), xb = cfg.wrap(base + q0 + q1, ip);
-  const f32x2 theta = {kTwoPiF * xa, kTwoPiF * xb};                       // vocoder.py:574
-  // table cis(j theta), j = 1..16, as (cos_A, cos_B) / (sin_A, sin_B) pairs
-  f32x2 tc[16], ts[16];
-  {
-    float c0, s0, c1, s1;
-    cis_product(1.0f, theta.x, c0, s0);
-    cis_product(1.0f, theta.y, c1, s1);
-    tc[0] = f32x2{c0, c1};
-    ts[0] = f32x2{s0, s1};
-#pragma unroll
-    for (int j = 1; j < 16; ++j) {
-      tc[j] = __builtin_elementwise_fma(tc[j - 1], tc[0], -(ts[j - 1] * ts[0]));
-      ts[j] = __builtin_elementwise_fma(ts[j - 1], tc[0], tc[j - 1] * ts[0]);
-    }
-  }
-  // interpolation weight of the thread's two samples (core.py:66-70: lambda = j / hop towards frame f + 1; exact in the
-  // shift form)
-  const f32x2 lam = {(float)(2 * tid) * up.scale, (float)(2 * tid + 1) * up.scale};
-  // sum_k sin(k theta) A_k(t) block by block:  sin((16 b + j) theta) = Cb sin(j theta) + Sb cos(j theta), so a block
-  // contributes Cb P + Sb Q with P = sum_j sin(j theta) A_j(t), Q = sum_j cos(j theta) A_j(t): three packed
-  // multiply-adds per harmonic and sample pair (amplitude interpolation, P, Q)
-  f32x2 S = {0.f, 0.f};
-  f32x2 Cb = {1.f, 1.f}, Sb = {0.f, 0.f};            // cis(16 b theta)
-  const int nblk = HP >> 4;
-  for (int blk = 0; blk < nblk; ++blk) {
-    if (blk > 0) {
-      if ((blk & 3) == 0) {                         // accurate re-seed
-        float c0, s0, c1, s1;
-        cis_product((float)(16 * blk), theta.x, c0, s0);
-        cis_product((float)(16 * blk), theta.y, c1, s1);
-        Cb = f32x2{c0, c1};
-        Sb = f32x2{s0, s1};
-      } else {                                      // rotate by cis(16 theta)
-        const f32x2 cn = __builtin_elementwise_fma(Cb, tc[15], -(Sb * ts[15]));
-        Sb = __builtin_elementwise_fma(Sb, tc[15], Cb * ts[15]);
-        Cb = cn;
-      }
-    }
-    const float4* ap = reinterpret_cast<const float4*>(amp + 32 * blk);   // (A, dA) of two harmonics per 16-byte read
-    f32x2 P = {0.f, 0.f}, Q = {0.f, 0.f};
-#pragma unroll
-    for (int jj = 0; jj < 8; ++jj) {
-      const float4 q = ap[jj];
-      // amplitude of the two samples: A + lambda dA with (A, dA) taken from the halves of ONE register pair (the compiler's
-      // own form of the second harmonic's interpolation copies dA into a fresh pair first: 8 v_mov per block)
-      const f32x2 a = lerp_pair(lam, f32x2{q.x, q.y});
-      const f32x2 b = lerp_pair(lam, f32x2{q.z, q.w});
-      P = __builtin_elementwise_fma(ts[2 * jj], a, P);
-      Q = __builtin_elementwise_fma(tc[2 * jj], a, Q);
-      P = __builtin_elementwise_fma(ts[2 * jj + 1], b, P);
-      Q = __builtin_elementwise_fma(tc[2 * jj + 1], b, Q);
-    }
-    S = __builtin_elementwise_fma(Cb, P, S);
-    S = __builtin_elementwise_fma(Sb, Q, S);
-  }
-  const float r[2] = {S.x, S.y};
-  float* dst = out + b * (long)F * HOP + t0;
-  if ((reinterpret_cast<uintptr_t>(dst) & 7) == 0) *reinterpret_cast<float2*>(dst) = make_float2(r[0], r[1]);
-  else { dst[0] = r[0]; dst[1] = r[1]; }
-}
-#endif  // DDSP_AB_GENERATIONS
-
 // ------------------------------------------------------------------------------------------------
 // sinusoid bank, mirrored-pair form (hop = 512; the default): blocks of 17 harmonics AROUND a centre c,
 //     a+ sin((c + j) theta) + a- sin((c - j) theta)  =  sin(c theta) cos(j theta) (a+ + a-)  +  cos(c theta) sin(j theta) (a+ - a-),
 // so with the frame's sums sigma_j = a(c+j) + a(c-j) and differences delta_j = a(c+j) - a(c-j) staged in LDS (they are
 // linear in the amplitudes, hence interpolate between the two frames exactly as the amplitudes do), a PAIR of harmonics
 // costs two interpolations and two multiply-adds: 2 packed instructions per harmonic and sample pair instead of the 3 of
-// k_sins_bank2 (amplitude interpolation, P, Q), and the table cis(j theta) has 8 entries instead of 16.  Block b has centre
-// c = 9 + 17 b and contributes  sin(c theta) (a_c + sum_j cos(j theta) sigma_j) + cos(c theta) sum_j sin(j theta) delta_j.
-// k_sins_bank2 was measured at 100 % vector-ALU occupancy (SQ_ACTIVE_INST_VALU = kernel cycles) and power-limited clocks:
-// only fewer multiply-adds make this kernel faster.  Harmonics beyond 17 * (H / 17) go into one more, zero-padded block,
-// or -- one or two of them -- are evaluated on their own.  Same numerics as k_sins_bank2 (sin(k theta) for the float32
-// theta without the reference's rounding of k * theta; accurate seeds every fourth block, rotations in between).
+// rounds 1 / 2's 16-harmonic blocks (amplitude interpolation, P, Q; retired, last in commit 08d7be1), and the table
+// cis(j theta) has 8 entries instead of 16.  Block b has centre c = 9 + 17 b and contributes
+//     sin(c theta) (a_c + sum_j cos(j theta) sigma_j) + cos(c theta) sum_j sin(j theta) delta_j.
+// The 16-harmonic form was measured at 100 % vector-ALU occupancy (SQ_ACTIVE_INST_VALU = kernel cycles) and power-limited
+// clocks: only fewer multiply-adds make this kernel faster.  Harmonics beyond 17 * (H / 17) go into one more, zero-padded
+// block, or -- one or two of them -- are evaluated on their own.  Numerics: sin(k theta) for the float32 theta without the
+// reference's rounding of k * theta; accurate seeds every fourth block, rotations in between.
 // ------------------------------------------------------------------------------------------------
 constexpr int SB3_J = 8;                              // pairs per block
 constexpr int SB3_W = 2 * SB3_J + 1;                  // harmonics per block: 17
@@ -413,114 +310,12 @@ __global__ void __launch_bounds__(256) k_sins_bank3(const float* __restrict__ f0
 // Adjoint of the sinusoid bank w.r.t. the amplitudes (hop = 512): for the frame of the workgroup,
 //     R0[k] = sum_t g[t] w0[t] sin(k theta_t)     (goes to amplitude row f)
 //     R1[k] = sum_t g[t] w1[t] sin(k theta_t)     (goes to amplitude row min(f+1, F-1))
-// The sines are generated exactly as in k_sins_bank2 (same table, same seeds); per block of 16 harmonics every
-// thread's 32 products (16 harmonics x two rows, its two samples already added) go through an LDS tile
-// [32][256 (+1 pad)] and are summed column-block-wise: thread (v = tid & 31, chunk = tid >> 5) adds 32 entries, the
-// two chunks of a wave meet by one cross-lane exchange, the four waves through a second small LDS array.
 // k_sins_bank_bwd_combine then forms dc[f][k] = A[f][k] (R0[f][k] + R1[f-1][k] (+ R1[F-1][k] on the last row)).
 // ------------------------------------------------------------------------------------------------
-#ifdef DDSP_AB_GENERATIONS                       // the LDS-tile adjoint the matrix-pipe form replaced: A/B builds only
-constexpr int SB_TILE_LD = 257;
-
-__global__ void __launch_bounds__(256) k_sins_bank2_bwd(const float* __restrict__ f0_frames,
-                                                        const float* __restrict__ initial_phase,
-                                                        const float* __restrict__ grad_out, int F, int H, Upsampler up,
-                                                        PhaseCfg cfg, const double* __restrict__ phase0,
-                                                        float* __restrict__ partial /* [B*F][HP][2] */) {
-  constexpr int HOP = 512;
-  __shared__ float tile[32 * SB_TILE_LD];
-  __shared__ float part[4][32];
-  __shared__ double wsum[4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const long fr = blockIdx.x;
-  const long b = fr / F;
-  const int f = (int)(fr - b * F);
-  const int HP = (H + 15) & ~15;
-  const float* f0_row = f0_frames + b * F;
-  const Upsampler::Row3 rows = up.load3(f0_row, f);
-  const float ip = cfg.has_ip ? initial_phase[b] : 0.0f;
-  const long t0 = (long)f * HOP + 2 * tid;
-  const double q0 = cfg.term(up.at3_in_frame(rows, 2 * tid, HOP));
-  const double q1 = cfg.term(up.at3_in_frame(rows, 2 * tid + 1, HOP));
-  const double mine = q0 + q1;
-  const double excl = wave_excl_scan(mine, lane);
-  if (lane == 63) wsum[wave] = excl + mine;
-  __syncthreads();
-  double base = phase0[fr] + excl;
-  for (int w = 0; w < wave; ++w) base += wsum[w];
-  const float xa = cfg.wrap(base + q0, ip), xb = cfg.wrap(base + q0 + q1, ip);
-  const f32x2 theta = {kTwoPiF * xa, kTwoPiF * xb};
-  f32x2 tc[16], ts[16];
-  {
-    float c0, s0, c1, s1;
-    cis_product(1.0f, theta.x, c0, s0);
-    cis_product(1.0f, theta.y, c1, s1);
-    tc[0] = f32x2{c0, c1};
-    ts[0] = f32x2{s0, s1};
-#pragma unroll
-    for (int j = 1; j < 16; ++j) {
-      tc[j] = __builtin_elementwise_fma(tc[j - 1], tc[0], -(ts[j - 1] * ts[0]));
-      ts[j] = __builtin_elementwise_fma(ts[j - 1], tc[0], tc[j - 1] * ts[0]);
-    }
-  }
-  // cotangent of the two samples times the interpolation weights of the two amplitude rows (core.py:66-70)
-  f32x2 gw0, gw1;
-  {
-    const float* gp = grad_out + b * (long)F * HOP + t0;
-    float w0[2], w1[2];
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      int i0, i1;
-      up.locate(t0 + q, i0, i1, w0[q], w1[q]);
-    }
-    gw0 = f32x2{gp[0] * w0[0], gp[1] * w0[1]};
-    gw1 = f32x2{gp[0] * w1[0], gp[1] * w1[1]};
-  }
-  f32x2 Cb = {1.f, 1.f}, Sb = {0.f, 0.f};
-  const int nblk = HP >> 4;
-  const int v = tid & 31, chunk = tid >> 5;
-  for (int blk = 0; blk < nblk; ++blk) {
-    if (blk > 0) {
-      if ((blk & 3) == 0) {
-        float c0, s0, c1, s1;
-        cis_product((float)(16 * blk), theta.x, c0, s0);
-        cis_product((float)(16 * blk), theta.y, c1, s1);
-        Cb = f32x2{c0, c1};
-        Sb = f32x2{s0, s1};
-      } else {
-        const f32x2 cn = __builtin_elementwise_fma(Cb, tc[15], -(Sb * ts[15]));
-        Sb = __builtin_elementwise_fma(Sb, tc[15], Cb * ts[15]);
-        Cb = cn;
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      const f32x2 sv = __builtin_elementwise_fma(Cb, ts[j], Sb * tc[j]);
-      const f32x2 p0 = sv * gw0, p1 = sv * gw1;
-      tile[(2 * j) * SB_TILE_LD + tid] = p0.x + p0.y;
-      tile[(2 * j + 1) * SB_TILE_LD + tid] = p1.x + p1.y;
-    }
-    __syncthreads();
-    float acc = 0.f;
-    const float* col = tile + v * SB_TILE_LD + chunk * 32;
-#pragma unroll
-    for (int i = 0; i < 32; ++i) acc += col[i];
-    acc += __shfl_xor(acc, 32);                                  // the wave's two chunks
-    if (lane < 32) part[wave][v] = acc;
-    __syncthreads();
-    if (tid < 32) {
-      const float tot = (part[0][tid] + part[1][tid]) + (part[2][tid] + part[3][tid]);
-      partial[(fr * HP + 16 * blk + (tid >> 1)) * 2 + (tid & 1)] = tot;
-    }
-    // the next block's tile writes come after this barrier pair; part[] is rewritten only after the next first barrier
-  }
-}
-#endif  // DDSP_AB_GENERATIONS
-
 // ------------------------------------------------------------------------------------------------
 // The same adjoint on the matrix pipe (hop = 512; the default).  R_r[k] = sum_t g[t] w_r[t] sin(k theta_t) is a reduction
-// over the 512 samples of the frame -- in k_sins_bank2_bwd every thread's products went through an LDS tile and two
-// barriers per 16 harmonics (0.79 ms against 0.22 ms forward).  With blocks of 33 harmonics around a centre c,
+// over the 512 samples of the frame -- in round 2's adjoint (retired, last in commit 08d7be1) every thread's products went
+// through an LDS tile and two barriers per 16 harmonics (0.79 ms against 0.22 ms forward).  With blocks of 33 harmonics around a centre c,
 //     sin((c +- j) theta) = sin(c theta) cos(j theta) +- cos(c theta) sin(j theta),   j = 1..16,
 // the sums are two small matrix products per frame,
 //     E[j][n] = sum_t cos(j theta_t) alpha_n[t],   O[j][n] = sum_t sin(j theta_t) beta_n[t],
@@ -728,14 +523,6 @@ int launch_sins_bank(const float* f0_frames, const float* initial_phase, const f
   PhaseCfg cfg = make_phase_cfg(sr, infer, initial_phase != nullptr);
   if (hop == 512 && up.shift > 0 && (long)B * F <= 0x7fffffffL && knob(KNOB_SINS_V1) != 1) {
     // block angle-addition forms: one workgroup per frame
-#ifdef DDSP_AB_GENERATIONS
-    if (knob(KNOB_SINS_V1) == 2) {                  // the 16-harmonic blocks of round 1 / 2 (same-box A/B builds)
-      const size_t sh2 = (size_t)2 * ((H + 15) & ~15) * sizeof(float);
-      hipLaunchKernelGGL(k_sins_bank2, dim3((unsigned)((long)B * F)), dim3(256), sh2, st, f0_frames, initial_phase, c_amp,
-                         ld_amp, F, H, up, cfg, phase0, out);
-      return 0;
-    }
-#endif
     // mirrored pairs around a centre, 17 harmonics per block; a remainder of one or two harmonics is evaluated on its own
     const int rem = H % SB3_W;
     const int nblk = H / SB3_W + (rem > 2 ? 1 : 0), nsingle = rem > 2 ? 0 : rem;
@@ -778,11 +565,6 @@ int launch_sins_bank_bwd(const float* f0_frames, const float* initial_phase, con
     else
       hipLaunchKernelGGL(k_sins_bank_bwd_any<32>, grid, block, 0, st, f0_frames, initial_phase, grad_out, F, hop, H, HP, up, cfg, phase0, scratch);
   }
-#ifdef DDSP_AB_GENERATIONS
-  else if (knob(KNOB_SINS_V1) != 0)
-    hipLaunchKernelGGL(k_sins_bank2_bwd, dim3((unsigned)((long)B * F)), dim3(256), 0, st, f0_frames, initial_phase, grad_out, F,
-                       H, up, cfg, phase0, scratch);
-#endif
   else                                                          // hop 512 (a power of two): the matrix-pipe form, one wave per frame
     hipLaunchKernelGGL(k_sins_bank_bwd_mfma, dim3((unsigned)((long)B * F)), dim3(64), 0, st, f0_frames, initial_phase, grad_out,
                        F, H, HP, up, cfg, phase0, scratch);

@@ -2,7 +2,7 @@
 // the kernel that has to live on 168 registers (k_fir_blk6, three waves per SIMD).
 //
 // fft_r.h keeps its exchanges conflict-free with XOR swizzles (tid ^ 2 n3, ...): eight distinct addresses per exchange that
-// the compiler either keeps in registers for the whole loop (k_fir_blk: ~40 of its 226) or recomputes every pass
+// the compiler either keeps in registers for the whole loop (round 3's two-wave filter kernel: ~40 of its 226) or recomputes every pass
 // (measured: +146 vector instructions per pass, which ate all that the third wave per SIMD had bought).  Here every exchange
 // is ONE base register plus instruction immediates:
 //     first exchange     [k1][p], rows of 128 words; odd rows with their 16-blocks swapped in pairs (two bases, as fft_r.h)
@@ -17,26 +17,6 @@
 
 namespace ddsp {
 namespace fft {
-
-// Timing experiments only (tools/gpu_r04.sh; results are WRONG under any of them): DDSP_ABL_NOLDS drops the exchange traffic,
-// DDSP_ABL_NOMATH the butterflies and twiddles, DDSP_ABL_NOBAR the barriers -- what each part of a pass costs beside the others.
-#if defined(DDSP_ABL_NOLDS)
-#define DDSP_P_ST(dst, val) do { } while (0)
-#define DDSP_P_LD(dst, src) do { } while (0)
-#else
-#define DDSP_P_ST(dst, val) (dst) = (val)
-#define DDSP_P_LD(dst, src) (dst) = rd(src)
-#endif
-#if defined(DDSP_ABL_NOMATH)
-#define DDSP_P_MATH(x) do { } while (0)
-#else
-#define DDSP_P_MATH(x) x
-#endif
-#if defined(DDSP_ABL_NOBAR)
-#define DDSP_P_SYNC() do { } while (0)
-#else
-#define DDSP_P_SYNC() __syncthreads()
-#endif
 
 struct Plan1024P {
   using Base = Plan<2>;
@@ -70,23 +50,15 @@ struct Plan1024P {
   // served in four 16-lane groups per half (8 LDS cycles for 16 bytes per lane) where two ds_read_b64 take 2 cycles each
   // (MI355X_MICROARCH.md, LDS table), and these layouts are conflict-free for the 32-lane form.  Measured [MI355X]
   // (profiles/r04_v2_*): SQ_LDS_IDX_ACTIVE 21.7 M -> 16.3 M cycles per launch, kernel alone 79.7 -> 76.1 us.
-  // (-DDDSP_P_PAIRED_READS: the compiler's pairing, for A/B runs)
+  // (The host form is the plain read: the CPU emulator has no LDS address space.)
   static __device__ __forceinline__ f32x2 rd(const f32x2* p) {
-#if !defined(DDSP_P_PAIRED_READS) && defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__)
     return *(const volatile __attribute__((address_space(3))) f32x2*)p;
 #else
     return *p;
 #endif
   }
 
-  // a read of a PARKED spectrum (own slot / mirror image): paired by the compiler unless DDSP_P_SINGLE_PARKED
-  static __device__ __forceinline__ f32x2 rd_parked(const f32x2* p) {
-#if defined(DDSP_P_SINGLE_PARKED) && defined(__HIP_DEVICE_COMPILE__)
-    return *(const volatile __attribute__((address_space(3))) f32x2*)p;
-#else
-    return *p;
-#endif
-  }
   static __device__ __forceinline__ int s_index(int tid, int slot) { return Base::s_index(tid, slot); }
   static __device__ __forceinline__ int parked(int k) { return Base::parked(k); }
   // Where thread tid finds the mirror image of its slot m, parked(-(s_index(tid, m)) mod 1024), as base - 64 m: with
@@ -103,30 +75,24 @@ struct Plan1024P {
   // return X is free and Y may still be read by slower waves.  HI_ZERO: v[4..7] are zero on entry.
   template <bool HI_ZERO = false, bool FLIP = false>
   static __device__ __forceinline__ void forward_s(f32x2 (&v)[8], const Tw& tw, f32x2* X, f32x2* Y, const Ix& ix) {
-    DDSP_P_MATH({
     if (HI_ZERO) dft8_lo4(v);
     else dft8(v);
     twiddle7(v, tw.w1);
-    });
 #pragma unroll
-    for (int k = 0; k < 8; ++k) DDSP_P_ST(X[k * P + ((k & 1) ? ix.w1b : ix.w1a)], v[k]);
-    DDSP_P_SYNC();
+    for (int k = 0; k < 8; ++k) X[k * P + ((k & 1) ? ix.w1b : ix.w1a)] = v[k];
+    __syncthreads();
 #pragma unroll
-    for (int n2 = 0; n2 < 8; ++n2) DDSP_P_LD(v[n2], X + ((n2 & 1) ? ix.r1o : ix.r1e) + n2 * C);
-    DDSP_P_MATH({
+    for (int n2 = 0; n2 < 8; ++n2) v[n2] = rd(X + ((n2 & 1) ? ix.r1o : ix.r1e) + n2 * C);
     dft8(v);
     twiddle7(v, tw.w2);
-    });
 #pragma unroll
-    for (int k2 = 0; k2 < 8; ++k2) DDSP_P_ST(Y[ix.w2 + k2 * C], v[k2]);
-    DDSP_P_SYNC();
+    for (int k2 = 0; k2 < 8; ++k2) Y[ix.w2 + k2 * C] = v[k2];
+    __syncthreads();
 #pragma unroll
-    for (int n3 = 0; n3 < 8; ++n3) DDSP_P_LD(v[n3], Y + n3 * S2 + ix.t);
-    DDSP_P_MATH({
+    for (int n3 = 0; n3 < 8; ++n3) v[n3] = rd(Y + n3 * S2 + ix.t);
     dft8(v);
     Base::apply_w3(v, tw, ix.t);
     Base::template lane_pair_dft2<FLIP>(v, ix.t);
-    });
   }
 
   // The inverse (layout S -> natural order, v) and one exchange behind it the forward transform of a zero-padded input
@@ -141,45 +107,37 @@ struct Plan1024P {
   template <bool FLIP = false, bool U_FULL = false>
   static __device__ __forceinline__ void transposed_then_forward_s(f32x2 (&v)[8], f32x2 (&u)[8], const Tw& tw, f32x2* Y, f32x2* X,
                                                                    f32x2* Q, const Ix& ix) {
-    DDSP_P_MATH({
     Base::template lane_pair_dft2<FLIP>(v, ix.t);
     Base::apply_w3(v, tw, ix.t);
     dft8(v);
-    });
 #pragma unroll
-    for (int k = 0; k < 8; ++k) DDSP_P_ST(Y[k * S3 + ix.t], v[k]);
-    DDSP_P_SYNC();
+    for (int k = 0; k < 8; ++k) Y[k * S3 + ix.t] = v[k];
+    __syncthreads();
 #pragma unroll
-    for (int k = 0; k < 8; ++k) DDSP_P_LD(v[k], Y + ix.r3 + k * C);
-    DDSP_P_MATH({
+    for (int k = 0; k < 8; ++k) v[k] = rd(Y + ix.r3 + k * C);
     if (U_FULL) dft8(u);
     else dft8_lo4(u);
     twiddle7x2(v, tw.w2, u, tw.w1);
     dft8(v);
-    });
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-      DDSP_P_ST(X[ix.w4 + k * C], v[k]);
-      DDSP_P_ST(Q[k * P + ((k & 1) ? ix.w1b : ix.w1a)], u[k]);
+      X[ix.w4 + k * C] = v[k];
+      Q[k * P + ((k & 1) ? ix.w1b : ix.w1a)] = u[k];
     }
-    DDSP_P_SYNC();
+    __syncthreads();
 #pragma unroll
-    for (int k = 0; k < 8; ++k) { DDSP_P_LD(v[k], X + k * P + ix.t); DDSP_P_LD(u[k], Q + ((k & 1) ? ix.r1o : ix.r1e) + k * C); }
-    DDSP_P_MATH({
+    for (int k = 0; k < 8; ++k) { v[k] = rd(X + k * P + ix.t); u[k] = rd(Q + ((k & 1) ? ix.r1o : ix.r1e) + k * C); }
     dft8(u);
     twiddle7x2(v, tw.w1, u, tw.w2);
     dft8(v);
-    });
 #pragma unroll
-    for (int k = 0; k < 8; ++k) DDSP_P_ST(Y[ix.w2 + k * C], u[k]);
-    DDSP_P_SYNC();
+    for (int k = 0; k < 8; ++k) Y[ix.w2 + k * C] = u[k];
+    __syncthreads();
 #pragma unroll
-    for (int k = 0; k < 8; ++k) DDSP_P_LD(u[k], Y + k * S2 + ix.t);
-    DDSP_P_MATH({
+    for (int k = 0; k < 8; ++k) u[k] = rd(Y + k * S2 + ix.t);
     dft8(u);
     Base::apply_w3(u, tw, ix.t);
     Base::template lane_pair_dft2<FLIP>(u, ix.t);
-    });
   }
 };
 

@@ -419,7 +419,7 @@ __global__ void __launch_bounds__(128, 3) k_fir_blk_bwd6(FirBwdJobs jobs, FirBwd
   const int kS0 = PL::s_index(tid, 0);
   const int kP0 = PL::parked(kS0);
   const int mb = PL::mirror_base(tid);
-  auto mirrored = [&](const f32x2* X, int m) -> f32x2 { return PL::rd_parked(X + mb - 64 * m); };
+  auto mirrored = [&](const f32x2* X, int m) -> f32x2 { return *(X + mb - 64 * m); };
   const bool own_mirror = tid < 2;
   auto park = [&](const f32x2 (&z)[S], f32x2* X) {
 #pragma unroll
@@ -465,7 +465,7 @@ __global__ void __launch_bounds__(128, 3) k_fir_blk_bwd6(FirBwdJobs jobs, FirBwd
     f32x2 M0;
 #pragma unroll
     for (int m = 0; m < S; m += 2) {
-      const f32x2 o0 = PL::rd_parked(bC + kP0 + 64 * m), o1 = PL::rd_parked(bC + kP0 + 64 * (m + 1));
+      const f32x2 o0 = *(bC + kP0 + 64 * m), o1 = *(bC + kP0 + 64 * (m + 1));
       f32x2 tn0 = mirrored(bC, m);
       const f32x2 tn1 = mirrored(bC, m + 1);
       if (m == 0) tn0 = own_mirror ? -o0 : tn0;

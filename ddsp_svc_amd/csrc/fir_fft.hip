@@ -2,20 +2,20 @@
 // does it -- per-frame block convolution in the frequency domain with overlap-add -- but as one fused
 // kernel whose spectra never leave the CU.
 //
-// Frame j (0..F, row F re-uses taps F-1, core.py:167) convolves its taps (N <= 512; 514 .. 1022 in the LONG variant) with the chunk
+// Frame j (0..F, row F re-uses taps F-1, core.py:167) convolves its taps (N <= 1022) with the chunk
 // (x * tri_j)[(j-1) hop .. (j+1) hop)  (the periodic Bartlett window of core.py:161 IS tri_j) and adds the
 // 2 hop + N - 1 results at output position (j-1) hop - N/2 (crop of core.py:113-117).  With hop = 512 and
-// N <= 512 the linear convolution (<= 1535 samples) fits a 2048-point transform without time aliasing
-// (core.py:165 pads to 1533) and two consecutive frames fit the 2048-sample overlap-add ring.
+// N <= 1022 the linear convolution (<= 2045 samples) fits a 2048-point transform without time aliasing
+// and two consecutive frames (<= 2557 samples) fit the 4096-sample overlap-add ring.
 //
 // Per PAIR of frames (j, j+1) a 256-thread workgroup runs three 2048-point complex FFTs (fft2048.h):
 //   Z_j   = FFT(chunk_j + i * s_j * taps_j)        two real sequences per transform; s_j = power of two that
 //   Z_j+1 = FFT(chunk_j+1 + i * s_j+1 * taps_j+1)   balances their magnitudes (exact to undo)
 //   G[k]  = (Z[k] + conj Z[-k]) (Z[k] - conj Z[-k]) / 4i  = X[k] H[k]          (Hermitian by construction)
 //   out_j + i out_j+1 = IFFT(G_j / s_j + i G_j+1 / s_j+1)                       (inverse = conj, forward, conj)
-// and adds both results into a 2048-sample overlap-add ring in LDS, from which finished samples are
-// streamed out.  A workgroup walks a run of consecutive pairs of one utterance; it starts one pair early
-// (whose output it discards) so the ring holds the tails of the frames before its first own pair.
+// and adds both results into the overlap-add ring in LDS, from which finished samples are
+// streamed out.  A workgroup walks a run of consecutive pairs of one utterance; it starts two pairs early
+// (whose output it discards) so the ring holds the tails of the four frames that reach into its first own pair.
 //
 // Cost: ~1.5 complex 2048-FFTs per frame (~170 kflop on the vector ALUs) against 2 hop N = 522 k
 // multiply-adds (1.04 Mflop, x1.29 tile waste) for the direct form on the MFMA pipe.
@@ -43,12 +43,14 @@ __device__ __forceinline__ f32x2 packed_product(f32x2 a, f32x2 zneg, f32x2 q) {
   return fft::swap_scale(p, q);
 }
 
-// LONG: tap counts from 514 to 1022 (n_mag up to 512: the harmonic filter of the classic CombSub configuration,
-// n_mag_allpass 256 / n_mag_harmonic 512 / n_mag_noise 256).  A frame's linear convolution (2 hop + N - 1 <= 2045 samples)
-// still fits the 2048-point transform; what grows is its reach: four taps per thread instead of two, all eight slots of the
-// result are live, two consecutive frames span up to 2557 samples (a 4096-sample ring: 48 KB of LDS, three workgroups per
-// CU), and a run needs TWO warm-up pairs for its ring to hold the tails of the four frames that reach into it.  Without this
-// form such a filter ran on the direct MFMA form at ~3x the time.
+// ONE form, LONG = true, for every tap count up to 1022 (n_mag up to 512: the harmonic filter of the classic CombSub
+// configuration, n_mag_allpass 256 / n_mag_harmonic 512 / n_mag_noise 256; without it such a filter ran on the direct MFMA form
+// at ~3x the time): four taps per thread, all eight slots of the result live, a 4096-sample ring (48 KB of LDS with the two
+// exchange buffers: three workgroups per CU) and TWO warm-up pairs per run.  Round 2's short form for N <= 512 (LONG = false: two
+// taps per thread, 2048-sample ring, one warm-up pair, four workgroups per CU) is retired and never instantiated (last launched
+// in commit 08d7be1).  The kernel stays a template with that one instantiation: written as a plain kernel it has the same
+// instructions but is assembled into .text instead of the instance's own section (profiles/one_form_device_digests.txt), and the
+// change that retired the other generations was to leave every device object as it was.
 template <bool LONG>
 __global__ void __launch_bounds__(fft::THREADS, LONG ? 3 : 4) k_fir_fft(const float* __restrict__ x, int x_is_u01,
                                                                      const float* __restrict__ taps,
@@ -209,17 +211,12 @@ __global__ void __launch_bounds__(fft::THREADS, LONG ? 3 : 4) k_fir_fft(const fl
 int launch_fir_fft(const float* x, int x_is_u01, const float* taps, const float* addend, float* out, float* out_plain,
                    int B, int F, int hop, int N, hipStream_t st) {
   if (hop != FF_HOP || N < 2 || (N & 1) || N > 1022 || (long)F * hop >= (1L << 30)) return -1;
-#ifdef DDSP_AB_GENERATIONS
-  const bool long_taps = N > 512;                 // A/B builds keep round 2's short form (two taps per thread, 2048-sample ring)
-#else
-  const bool long_taps = true;                    // ONE form: four taps per thread, 4096-sample ring -- every N up to 1022
-#endif
   FirFftGeom g;
   g.F = F; g.N = N; g.T = F * hop;
   g.pairs = (F + 2) / 2;
-  // run length (own pairs per workgroup): as many workgroups as the chip holds at once (4 per CU at this
-  // kernel's LDS budget), so all of them run in one round with equal work; every run pays one warm-up pair
-  const long slots = (long_taps ? 3 : 4) * 256;
+  // run length (own pairs per workgroup): as many workgroups as the chip holds at once (3 per CU at this
+  // kernel's LDS budget), so all of them run in one round with equal work; every run pays two warm-up pairs
+  const long slots = 3 * 256;
   const int Bg = t_geometry_batch > 0 ? t_geometry_batch : B;          // kernels.h: a sub-batch keeps the whole call's split
   long per_utt = slots / (Bg > 0 ? Bg : 1);
   if (per_utt < 1) per_utt = 1;
@@ -231,12 +228,6 @@ int launch_fir_fft(const float* x, int x_is_u01, const float* taps, const float*
   g.runs_per_utt = (g.pairs + run - 1) / run;
   const long wgs = (long)B * g.runs_per_utt;
   if (wgs > 0x7fffffffL) return -1;
-#ifdef DDSP_AB_GENERATIONS
-  if (!long_taps) {
-    hipLaunchKernelGGL(k_fir_fft<false>, dim3((unsigned)wgs), dim3(fft::THREADS), 0, st, x, x_is_u01, taps, addend, out, out_plain, g);
-    return 4;
-  }
-#endif
   hipLaunchKernelGGL(k_fir_fft<true>, dim3((unsigned)wgs), dim3(fft::THREADS), 0, st, x, x_is_u01, taps, addend, out, out_plain, g);
   return 4;
 }

@@ -40,21 +40,11 @@ __global__ void k_set_pfa_timeline(long long* p) { g_pfa_timeline = p; }
 
 namespace pfa {
 
-// the 16-byte store of four taps (A/B builds: -DDDSP_PFA_NT = with the non-temporal policy)
-typedef float v4f_t __attribute__((ext_vector_type(4)));
+// the 16-byte store of four taps
 __device__ __forceinline__ void store4(float* p, float a, float b, float c, float d) {
-#ifdef DDSP_PFA_NT
-  __builtin_nontemporal_store(v4f_t{a, b, c, d}, reinterpret_cast<v4f_t*>(p));
-#else
   *reinterpret_cast<float4*>(p) = make_float4(a, b, c, d);
-#endif
 }
 
-#ifdef DDSP_PFA_NT_LD
-#define PFA_LD(p) __builtin_nontemporal_load(p)
-#else
-#define PFA_LD(p) (*(p))
-#endif
 constexpr int NB = 256, NT = 510, HALF = 255;
 #ifndef DDSP_PFA_ROWS
 #define DDSP_PFA_ROWS 16
@@ -392,7 +382,7 @@ __device__ __forceinline__ void taps_pfa510_body(const TapsJobs& jobs, const Exc
       if (live) {
         const float* src = a_re + gr * ld_re + k;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[q][e] = PFA_LD(src + e);
+        for (int e = 0; e < 4; ++e) v[q][e] = src[e];
         if (KIND == KIND_COMPLEX) {
           const float* si = a_im + gr * ld_im + k;
 #pragma unroll
@@ -431,12 +421,8 @@ __device__ __forceinline__ void taps_pfa510_body(const TapsJobs& jobs, const Exc
   // computed (128 threads: two full waves instead of four), and stage B computes rows k1 = 0 .. 8 only -- row 17 - k1 is the same
   // numbers at the mirrored taps -- reading the missing columns from the mirrored row and writing every result twice.  (Round 2
   // built this when a launch's length was set by its latencies and it did not pay; in the fused front launch, which runs at the
-  // vector pipe's rate, it does: EXPERIMENTS 6.8.  -DDDSP_PFA_NOSYM: the full form, for A/Bs.)
-#ifdef DDSP_PFA_NOSYM
-  const bool sym = false;
-#else
+  // vector pipe's rate, it does: EXPERIMENTS 6.8.)
   const bool sym = KIND == KIND_REAL;                       // workgroup-uniform
-#endif
   {
     const bool act = sym ? tid < TR * 16 : tid < TR * 30;
     const int t = !act ? 0 : (sym ? tid >> 4 : tid / 30), n2 = !act ? 0 : (sym ? tid & 15 : tid - 30 * t);
@@ -951,9 +937,6 @@ int launch_taps_pfa510(const float* a_re, long ld_re, const float* a_im, long ld
     kind = pfa::KIND_COMPLEX;
   }
   const int m = mode == pfa::MODE_HANN ? pfa::MODE_HANN : (mode == pfa::MODE_DYNAMIC ? pfa::MODE_DYNAMIC : pfa::MODE_ROLL);
-#ifdef DDSP_PFA_NOSYM
-  if (half_rows) return -1;
-#endif
   if (half_rows && (kind != pfa::KIND_REAL || m == pfa::MODE_DYNAMIC)) return -1;   // a zero-phase response under an even window (the dynamic one clamps one side only, core.py:245)
   TapsJob job{kind, act == 1 ? 1 : 0, m, a_re, ld_re, a_im, ld_im, scale, hann, half_width, hw_from_f0_sr, rows, taps, half_rows ? 1 : 0};
   if (batch) {                                              // collected, launched by launch_taps_pfa510_batch (all jobs: the same row count)

@@ -13,6 +13,9 @@ enum Knob {
   KNOB_AP_BWD_SPLIT, KNOB_SINS_SEQ, KNOB_BATCH_SPLIT,
   KNOB_COUNT
 };
+// RETIRED (the names stay in the table so that a stale script fails loudly): BLK_WPS and BLK_PADLDS chose and probed round 3's
+// two-wave hop-block filter, SINS_V1 = 2 the 16-harmonic sinusoid bank and its adjoint.  Those kernels are gone; any non-zero
+// BLK_WPS / BLK_PADLDS and SINS_V1 = 2 are refused (api.hip, knob_is_inert).  SINS_V1 = 1 (the generic bank) is live.
 
 // a step with fewer frames than this (B F) takes the streaming-shape forms: fewer, fused launches (knob SMALL_PATH = 1: never)
 constexpr long kSmallRows = 4096;

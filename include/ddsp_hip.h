@@ -63,10 +63,10 @@ const char* ddsp_hip_error_string(int code);
  * it (0 = built-in default).  No reference counterpart: measurement tools and the run-split tests use them.
  * Knobs that choose between forms of one operation: TAPS_GEMM (tap synthesis and its adjoint: 0 = by bin count -- prime
  * factors at 256, chirp-z from 112 to 1025, the dense contraction elsewhere; 1 = the dense contraction everywhere;
- * 2 = chirp-z wherever its plans reach), SINS_V1 (sinusoid bank generations), STFT_WPS (waves per SIMD of the short-time
+ * 2 = chirp-z wherever its plans reach), SINS_V1 (1 = the generic sinusoid bank at every hop; 2 is retired and refused), STFT_WPS (waves per SIMD of the short-time
  * spectral filter's variants), CZT_ROUNDS (rounds of resident workgroups of the loss kernels), CZT_TURNS (priority turns of a SIMD's waves in the loss's
- * backward kernel: 0 = on, 2 = off), BLK_WPS (the hop-block filter: 0 / 3 = k_fir_blk6, three waves per SIMD; 2 = round 3's
- * two-wave kernel, kept for same-box A/B runs), SINS_NOSKIP (1 = the sinusoid bank also sums the harmonics that are masked
+ * backward kernel: 0 = on, 2 = off), BLK_WPS and BLK_PADLDS (retired with round 3's two-wave hop-block filter: any non-zero
+ * value is refused, -1 from set_tuning and a warning from the environment), SINS_NOSKIP (1 = the sinusoid bank also sums the harmonics that are masked
  * to 1e-7 in both frames of a hop), SMALL_PATH (1 = never take the fused launches of the streaming shapes, B F < 4096: the
  * batch layout at every size; the results are the same bits either way), TAPS_FULL (1 = the fused layouts keep the noise
  * filter's tap rows whole, [B,F,N], instead of their first N/2 + 1 taps -- an even response; same bits either way),

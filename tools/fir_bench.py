@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Time the FIR kernel variants with events on the launch stream (B=32 x 10 s, N=510), incl. env-selected
-sub-variants of the hop-block FFT form (DDSP_HIP_BLK_WPS, DDSP_HIP_BLK_RUN)."""
+run lengths of the hop-block FFT form (RUNS="0 2 4": knob BLK_RUN)."""
 import json
 import os
 import sys
@@ -37,16 +37,8 @@ def timeit(impl, reps=20):
 
 res = {"impl3_mfma8_ms": timeit(3), "impl4_fft2048_ms": timeit(4)}
 y4 = y.clone()
-for wps in os.environ.get("WPS", "3").split():            # (2: only in a -DDDSP_AB_GENERATIONS build; the product library refuses the knob)
-    try:
-        _ffi.set_tuning("BLK_WPS", int(wps) if wps != "3" else 0)
-    except RuntimeError:
-        continue
-    for run in os.environ.get("RUNS", "0").split():
-        if run != "0":
-            _ffi.set_tuning("BLK_RUN", int(run))
-        else:
-            _ffi.set_tuning("BLK_RUN", 0)
-        res["impl5_blk_wps%s_run%s_ms" % (wps, run)] = timeit(5)
+for run in os.environ.get("RUNS", "0").split():
+    _ffi.set_tuning("BLK_RUN", int(run))
+    res["impl5_blk_run%s_ms" % run] = timeit(5)
 res["rel_rms_impl5_vs_impl4"] = float(((y - y4).double().pow(2).mean().sqrt() / y4.double().pow(2).mean().sqrt()))
 print(json.dumps(res, indent=1))
