@@ -19,7 +19,6 @@ using namespace ddsp;
 
 // ---- tuning knobs (csrc/tuning.h): environment read once, afterwards only ddsp_hip_set_tuning() ----------------------
 namespace ddsp {
-thread_local int t_geometry_batch = 0;
 namespace {
 const char* const kKnobNames[KNOB_COUNT] = {"BLK_WPS", "BLK_RUN", "BLK_PADLDS", "FFT_RUN", "STFT_WPS", "STFT_RUN",
                                             "MEL_WPS", "MEL_RUN", "FIR_MAX_SLOTS", "SINS_V1", "TAPS_GEMM", "STREAM_LAYOUT",
@@ -113,7 +112,7 @@ struct BranchEvents {
 
 // The HIP objects this library creates (fork / join events, the second lane's streams) live in ONE process-wide pool per device:
 // a call checks a set out and hands it back when it returns, so their number is bounded by the calls in flight at once -- not by
-// the host threads that ever called (rounds 2 - 5 kept them in thread_local arrays without destructors: a caller on short-lived
+// the host threads that ever called (rounds 2 - 5 kept them in per-thread arrays without destructors: a caller on short-lived
 // threads leaked a set per thread).  A set that goes back while its work is still in flight is safe to re-use: a wait captures
 // the record that precedes it, and streams order whatever the next user enqueues behind it.  Nothing is destroyed at exit.
 template <class T>
@@ -258,20 +257,19 @@ LaneSet* second_lane(int* dev_out) {
   return &l;
 }
 
-// Whether this call uses the dense contraction at 256 bins too (knob TAPS_GEMM): read ONCE per entry point into this
-// thread-local, so that the stream layout and every tap synthesis of one call agree even if another thread changes
+// Which form the tap syntheses of a call take (knob TAPS_GEMM): read ONCE per entry point into this value, which the call
+// hands down, so that the stream layout and every tap synthesis of one call agree even if another thread changes
 // the knob meanwhile (a disagreement would let the fallback stage the all-pass response in a buffer the layout has
 // already given to the exciter).
-thread_local bool t_taps_gemm = false;
-thread_local int t_czt_from = 112;          // chirp-z form from this bin count on (below it the dense contraction is the faster one:
+struct TapsForm {
+  bool gemm;                                // the dense contraction at 256 bins too
+  int czt_from;                             // chirp-z form from this bin count on (below it the dense contraction is the faster one:
                                             // its cost falls with n^2, the 512-point plan's does not; equal at ~120 bins, measured)
-struct TapsFormScope {
-  TapsFormScope() {
-    const long v = knob(KNOB_TAPS_GEMM);     // 0: by shape; 1: the dense contraction everywhere; 2: chirp-z wherever its plans reach
-    t_taps_gemm = v == 1;
-    t_czt_from = v == 2 ? 2 : 112;
-  }
 };
+TapsForm taps_form() {
+  const long v = knob(KNOB_TAPS_GEMM);       // 0: by shape; 1: the dense contraction everywhere; 2: chirp-z wherever its plans reach
+  return TapsForm{v == 1, v == 2 ? 2 : 112};
+}
 
 // the periodic Hann behind the two basis planes of the table (k_ir_table, ir.hip)
 const float* table_hann(const float* table, int n) {
@@ -281,12 +279,13 @@ const float* table_hann(const float* table, int n) {
 
 // tap synthesis of one filter: the prime-factor form when the shape is its (n_mag = 256), the chirp-z form for the other bin
 // counts from 112 to 1025, else (or under knob TAPS_GEMM = 1) the dense contraction
-void synth_taps(const float* a_re, long ld_re, const float* a_im, long ld_im, int act, float scale, const float* table,
-                int mode, const float* half_width, long rows, int n, float* taps, hipStream_t st, float hw_sr = 0.f) {
-  if (!t_taps_gemm &&
+void synth_taps(const TapsForm& form, const float* a_re, long ld_re, const float* a_im, long ld_im, int act, float scale,
+                const float* table, int mode, const float* half_width, long rows, int n, float* taps, hipStream_t st,
+                float hw_sr = 0.f) {
+  if (!form.gemm &&
       launch_taps_pfa510(a_re, ld_re, a_im, ld_im, 0, act, scale, table, mode, half_width, rows, n, taps, st, hw_sr) == 0)
     return;
-  if (!t_taps_gemm && n != 256 && n >= t_czt_from &&
+  if (!form.gemm && n != 256 && n >= form.czt_from &&
       launch_taps_czt(a_re, ld_re, a_im, ld_im, act, scale, table_hann(table, n), mode, half_width, rows, n, taps, st, hw_sr) == 0)
     return;
   launch_ir_gemm(a_re, ld_re, a_im, ld_im, act, scale, table, mode, half_width, rows, n, taps, st, hw_sr);
@@ -294,16 +293,28 @@ void synth_taps(const float* a_re, long ld_re, const float* a_im, long ld_im, in
 
 // all-pass taps from the raw group-delay control (vocoder.py:581,599 / :834,845): fused in the prime-factor kernel, else
 // response (re, im scratch of rows * n floats each) + dense contraction
-void synth_allpass_taps(const float* c_gd, long ld_gd, const float* table, long rows, int n, float* re, float* im,
-                        float* taps, hipStream_t st) {
-  if (!t_taps_gemm && launch_taps_pfa510(c_gd, ld_gd, nullptr, 0, 1, DDSP_HIP_ACT_NONE, 1.0f, table, DDSP_HIP_MODE_ROLL, nullptr,
+void synth_allpass_taps(const TapsForm& form, const float* c_gd, long ld_gd, const float* table, long rows, int n, float* re,
+                        float* im, float* taps, hipStream_t st) {
+  if (!form.gemm && launch_taps_pfa510(c_gd, ld_gd, nullptr, 0, 1, DDSP_HIP_ACT_NONE, 1.0f, table, DDSP_HIP_MODE_ROLL, nullptr,
                                          rows, n, taps, st) == 0)
     return;
   launch_allpass_response(c_gd, ld_gd, rows, n, re, im, st);
-  if (!t_taps_gemm && n != 256 && n >= t_czt_from &&
+  if (!form.gemm && n != 256 && n >= form.czt_from &&
       launch_taps_czt(re, n, im, n, DDSP_HIP_ACT_NONE, 1.0f, table_hann(table, n), DDSP_HIP_MODE_ROLL, nullptr, rows, n, taps, st, 0.f) == 0)
     return;
   launch_ir_gemm(re, n, im, n, DDSP_HIP_ACT_NONE, 1.0f, table, DDSP_HIP_MODE_ROLL, nullptr, rows, n, taps, st);
+}
+
+// the adjoint of synth_taps: the prime-factor form at 256 bins, the chirp-z form at the other bin counts up to 1025, else the
+// dense contraction
+void synth_taps_bwd(const TapsForm& form, const float* d_taps, const float* ctrl, long ld_ctrl, int act, float scale,
+                    const float* table, int mode, const float* half_width, long rows, int n, float* d_re, float* d_im,
+                    hipStream_t st) {
+  const bool fast = !form.gemm &&
+      (launch_taps_pfa510_bwd(d_taps, ctrl, ld_ctrl, act, scale, table, mode, half_width, rows, n, d_im != nullptr, d_re, d_im, st) == 0 ||
+       (n != 256 && n >= form.czt_from &&
+        launch_taps_czt_bwd(d_taps, ctrl, ld_ctrl, act, scale, table_hann(table, n), mode, half_width, rows, n, d_re, d_im, st) == 0));
+  if (!fast) launch_ir_gemm_bwd(d_taps, ctrl, ld_ctrl, act, scale, table, mode, half_width, rows, n, d_im != nullptr, d_re, d_im, st);
 }
 
 // knob STREAM_LAYOUT = 1 / 4: batch shapes keep the two-stream layouts of rounds 2 - 5 (A/B runs); default: the fused layout
@@ -314,8 +325,8 @@ bool fused_off() {
 
 // does a CombSub / Sins call of this shape take the fused one-stream layout (combsub_rows / sins_rows)?  One predicate for the
 // launch path and for ddsp_hip_tail_layout, which tells a training caller where the call left its intermediates.
-bool fused_shape_ok(long R, int F, int hop, int n0, int n1, int n2, int fir_impl, bool combsub) {
-  if (!(R < kSmallRows || !fused_off()) || hop != 512 || t_taps_gemm || knob(KNOB_SMALL_PATH) == 1) return false;
+bool fused_shape_ok(const TapsForm& form, long R, int F, int hop, int n0, int n1, int n2, int fir_impl, bool combsub) {
+  if (!(R < kSmallRows || !fused_off()) || hop != 512 || form.gemm || knob(KNOB_SMALL_PATH) == 1) return false;
   if (combsub) {
     // (an in-kernel noise draw changes nothing here: it rides in the paired filter launch as its second job)
     if (n0 != 256 || n1 != 256 || n2 != 256 || !(fir_impl == 0 || fir_impl == 5)) return false;
@@ -431,8 +442,7 @@ int ddsp_hip_impulse_response(const float* resp_re, long ld_re, const float* res
   if (rows == 0) return 0;
   if (!resp_re || !table || !taps) return DDSP_HIP_EINVAL;
   if (mode == DDSP_HIP_MODE_DYNAMIC && !half_width) return DDSP_HIP_EINVAL;
-  const TapsFormScope form;
-  synth_taps(resp_re, ld_re, resp_im, ld_im, act, scale, table, mode, half_width, rows, n_mag, taps, S(stream));
+  synth_taps(taps_form(), resp_re, ld_re, resp_im, ld_im, act, scale, table, mode, half_width, rows, n_mag, taps, S(stream));
   return finish();
 }
 
@@ -449,8 +459,7 @@ int ddsp_hip_allpass_taps(const float* c, long ld, long rows, int n_mag, const f
   if (scratch_bytes < ddsp_hip_allpass_taps_scratch_bytes(rows, n_mag)) return DDSP_HIP_EWS;
   float* re = static_cast<float*>(scratch);
   float* im = reinterpret_cast<float*>(static_cast<char*>(scratch) + align_up((size_t)rows * n_mag * sizeof(float), 256));
-  const TapsFormScope form;
-  synth_allpass_taps(c, ld, table, rows, n_mag, re, im, taps, S(stream));
+  synth_allpass_taps(taps_form(), c, ld, table, rows, n_mag, re, im, taps, S(stream));
   return finish();
 }
 
@@ -463,16 +472,7 @@ int ddsp_hip_impulse_response_backward(const float* d_taps, const float* ctrl, l
   if (act == DDSP_HIP_ACT_EXP && (!ctrl || ld_ctrl < n_mag)) return DDSP_HIP_EINVAL;
   if (mode == DDSP_HIP_MODE_DYNAMIC && !half_width) return DDSP_HIP_EINVAL;
   if (d_im && act != DDSP_HIP_ACT_NONE) return DDSP_HIP_ESHAPE;
-  const TapsFormScope form;
-  // the prime-factor form at 256 bins, the chirp-z form at the other bin counts up to 1025, else the dense contraction
-  const bool fast = !t_taps_gemm &&
-      (launch_taps_pfa510_bwd(d_taps, ctrl, ld_ctrl, act, scale, table, mode, half_width, rows, n_mag, d_im != nullptr, d_re, d_im,
-                              S(stream)) == 0 ||
-       (n_mag != 256 && n_mag >= t_czt_from && launch_taps_czt_bwd(d_taps, ctrl, ld_ctrl, act, scale, table_hann(table, n_mag), mode, half_width, rows,
-                                            n_mag, d_re, d_im, S(stream)) == 0));
-  if (!fast)
-    launch_ir_gemm_bwd(d_taps, ctrl, ld_ctrl, act, scale, table, mode, half_width, rows, n_mag, d_im != nullptr, d_re, d_im,
-                       S(stream));
+  synth_taps_bwd(taps_form(), d_taps, ctrl, ld_ctrl, act, scale, table, mode, half_width, rows, n_mag, d_re, d_im, S(stream));
   return finish();
 }
 
@@ -529,8 +529,7 @@ int ddsp_hip_frequency_filter(const float* audio, const float* resp_re, long ld_
   if (ws_bytes < ddsp_hip_frequency_filter_workspace_bytes(B, F, n_mag)) return DDSP_HIP_EWS;
   float* taps = static_cast<float*>(ws);
   const long R = (long)B * F;
-  const TapsFormScope form;
-  synth_taps(resp_re, ld_re, resp_im, ld_im, DDSP_HIP_ACT_NONE, 1.0f, table, mode, half_width, R, n_mag, taps, S(stream));
+  synth_taps(taps_form(), resp_re, ld_re, resp_im, ld_im, DDSP_HIP_ACT_NONE, 1.0f, table, mode, half_width, R, n_mag, taps, S(stream));
   if (launch_fir(audio, 0, taps, nullptr, out, nullptr, B, F, hop, 2 * (n_mag - 1), DDSP_HIP_FIR_AUTO, S(stream)) < 0)
     return DDSP_HIP_ESHAPE;
   return finish();
@@ -605,6 +604,9 @@ struct TailCall {
   float* signal; float* harmonic; float* noise_out;
   int fir_impl;
   NoiseGen gen;
+  TapsForm form;                      // one reading of knob TAPS_GEMM for the whole call
+  int geometry_batch;                 // the WHOLE call's B, in a sub-batch too (rows_of leaves it): the filters split an utterance
+                                      // into runs as the unsplit call would (run_split.h)
 };
 
 TailCall rows_of(const TailCall& a, int b0, int Bn) {
@@ -648,7 +650,6 @@ int run_lanes(const TailCall& a, const LanePlan& p, void* ws, size_t ws_bytes, i
     }
   }
   int rc = 0;
-  t_geometry_batch = a.B;                                // the filters split an utterance into runs as the unsplit call would
   for (int k = 0; k < p.nsub; ++k) {
     const int b0 = k * p.Bs, Bn = a.B - b0 < p.Bs ? a.B - b0 : p.Bs;
     const TailCall sub = rows_of(a, b0, Bn);
@@ -657,7 +658,6 @@ int run_lanes(const TailCall& a, const LanePlan& p, void* ws, size_t ws_bytes, i
     if (r != 0 && rc == 0) rc = r;
     if (rc != 0) break;
   }
-  t_geometry_batch = 0;
   if (lane1) {                                           // always joined, also on the error path
     (void)hipEventRecord(lane1->join, lane1->main1);
     (void)hipStreamWaitEvent(st, lane1->join, 0);
@@ -668,13 +668,13 @@ int run_lanes(const TailCall& a, const LanePlan& p, void* ws, size_t ws_bytes, i
 
 // the batch layout of the Sins tail (vocoder.py:580-611) on one (sub-)batch
 int sins_rows(const TailCall& a, SynthWs& w, hipStream_t st, void* aux_stream) {
-  const int B = a.B, F = a.F, hop = a.hop, H = a.n0, n_ap = a.n1, n_nz = a.n2;
+  const int B = a.B, F = a.F, hop = a.hop, H = a.n0, n_ap = a.n1, n_nz = a.n2, Bg = a.geometry_batch;
   const long R = (long)B * F;
   float* nz = a.noise_out ? a.noise_out : w.nzbuf;
   // The fused layout (as combsub_rows below; round 6: at every shape): both tap syntheses in one launch -- four dependent
   // launches on the caller's stream: sinusoid bank | taps (grid.y) | noise filter | all-pass filter + noise.  Same kernels, same
   // arguments, same bits as the two-stream layout below.  [MI355X] B = 32 x 10 s, same box: 0.3367 -> 0.3212 ms (r06_v10s_*).
-  if (fused_shape_ok(R, F, hop, H, n_ap, n_nz, a.fir_impl, false)) {
+  if (fused_shape_ok(a.form, R, F, hop, H, n_ap, n_nz, a.fir_impl, false)) {
     const int r = launch_sins_bank(a.f0_frames, a.initial_phase, a.c0, a.ld0, B, F, hop, H, a.sr, a.infer, a.phase0, w.buf0, st);
     if (r == -1) return DDSP_HIP_EHOP;
     if (r == -2) return DDSP_HIP_ESHAPE;
@@ -692,15 +692,15 @@ int sins_rows(const TailCall& a, SynthWs& w, hipStream_t st, void* aux_stream) {
     // draw, not at other tap counts than the noise filter's (one geometry per launch).
     if (half && !a.gen.on && n_ap == n_nz && knob(KNOB_SINS_SEQ) != 1) {
       const FirSecond second{w.buf0, 0, w.taps, nz, a.signal, a.harmonic, 0, 1};
-      if (launch_fir_blk(a.noise, a.noise_is_u01, w.taps_nz, nullptr, nz, nullptr, B, F, hop, 2 * (n_nz - 1), st, nullptr, &second, 1) >= 0)
+      if (launch_fir_blk(a.noise, a.noise_is_u01, w.taps_nz, nullptr, nz, nullptr, B, F, hop, 2 * (n_nz - 1), st, nullptr, &second, 1, Bg) >= 0)
         return 0;
     }
     if (half) {
-      if (launch_fir_blk(a.noise, a.noise_is_u01, w.taps_nz, nullptr, nz, nullptr, B, F, hop, 2 * (n_nz - 1), st, &a.gen, nullptr, 1) < 0)
+      if (launch_fir_blk(a.noise, a.noise_is_u01, w.taps_nz, nullptr, nz, nullptr, B, F, hop, 2 * (n_nz - 1), st, &a.gen, nullptr, 1, Bg) < 0)
         return DDSP_HIP_ESHAPE;
-    } else if (launch_fir(a.noise, a.noise_is_u01, w.taps_nz, nullptr, nz, nullptr, B, F, hop, 2 * (n_nz - 1), a.fir_impl, st, &a.gen) < 0)
+    } else if (launch_fir(a.noise, a.noise_is_u01, w.taps_nz, nullptr, nz, nullptr, B, F, hop, 2 * (n_nz - 1), a.fir_impl, st, &a.gen, Bg) < 0)
       return DDSP_HIP_ESHAPE;
-    if (launch_fir(w.buf0, 0, w.taps, nz, a.signal, a.harmonic, B, F, hop, 2 * (n_ap - 1), a.fir_impl, st) < 0)
+    if (launch_fir(w.buf0, 0, w.taps, nz, a.signal, a.harmonic, B, F, hop, 2 * (n_ap - 1), a.fir_impl, st, nullptr, Bg) < 0)
       return DDSP_HIP_ESHAPE;
     return 0;
   }
@@ -708,29 +708,29 @@ int sins_rows(const TailCall& a, SynthWs& w, hipStream_t st, void* aux_stream) {
   Branch br(st, aux_stream);           // without a second stream br.aux is the caller's stream: the same launches, in line
   // With the all-pass at 256 bins (prime-factor kernel: no response scratch in the exciter buffer) its taps go to the
   // second stream too, ahead of the noise branch, and the sinusoid bank starts at once (knob STREAM_LAYOUT 1: round-1 order)
-  const bool ap_ahead = n_ap == 256 && !t_taps_gemm && knob(KNOB_STREAM_LAYOUT) != 1;
-  if (ap_ahead) synth_allpass_taps(a.c1, a.ld1, a.t1, R, n_ap, w.re, w.im, w.taps, br.aux);
-  synth_taps(a.c2, a.ld2, nullptr, 0, DDSP_HIP_ACT_EXP, 1.0f / 128.0f, a.t2, DDSP_HIP_MODE_HANN, nullptr, R,
+  const bool ap_ahead = n_ap == 256 && !a.form.gemm && knob(KNOB_STREAM_LAYOUT) != 1;
+  if (ap_ahead) synth_allpass_taps(a.form, a.c1, a.ld1, a.t1, R, n_ap, w.re, w.im, w.taps, br.aux);
+  synth_taps(a.form, a.c2, a.ld2, nullptr, 0, DDSP_HIP_ACT_EXP, 1.0f / 128.0f, a.t2, DDSP_HIP_MODE_HANN, nullptr, R,
              n_nz, w.taps_nz, br.aux);
   const int rn = launch_fir(a.noise, a.noise_is_u01, w.taps_nz, nullptr, nz, nullptr, B, F, hop, 2 * (n_nz - 1), a.fir_impl,
-                            br.aux, &a.gen);
-  if (!ap_ahead) synth_allpass_taps(a.c1, a.ld1, a.t1, R, n_ap, w.re, w.im, w.taps, st);
+                            br.aux, &a.gen, Bg);
+  if (!ap_ahead) synth_allpass_taps(a.form, a.c1, a.ld1, a.t1, R, n_ap, w.re, w.im, w.taps, st);
   // exciter: sinusoid bank (vocoder.py:585-594)
   const int r = launch_sins_bank(a.f0_frames, a.initial_phase, a.c0, a.ld0, B, F, hop, H, a.sr, a.infer, a.phase0, w.buf0, st);
   br.join();                                           // always joined, also on the error paths below
   if (r == -1) return DDSP_HIP_EHOP;
   if (r == -2 || rn < 0) return DDSP_HIP_ESHAPE;
   // harmonic = all-pass(sinusoids) (vocoder.py:597-600); signal = harmonic + noise (:609)
-  if (launch_fir(w.buf0, 0, w.taps, nz, a.signal, a.harmonic, B, F, hop, 2 * (n_ap - 1), a.fir_impl, st) < 0)
+  if (launch_fir(w.buf0, 0, w.taps, nz, a.signal, a.harmonic, B, F, hop, 2 * (n_ap - 1), a.fir_impl, st, nullptr, Bg) < 0)
     return DDSP_HIP_ESHAPE;
   return 0;
 }
 
 // the batch layout of the CombSub tail (vocoder.py:834-862) on one (sub-)batch
 int combsub_rows(const TailCall& a, SynthWs& w, hipStream_t st, void* aux_stream) {
-  const int B = a.B, F = a.F, hop = a.hop, n_ap = a.n0, n_harm = a.n1, n_nz = a.n2;
+  const int B = a.B, F = a.F, hop = a.hop, n_ap = a.n0, n_harm = a.n1, n_nz = a.n2, Bg = a.geometry_batch;
   const long R = (long)B * F;
-  const bool all256 = n_ap == 256 && n_harm == 256 && n_nz == 256 && !t_taps_gemm;
+  const bool all256 = n_ap == 256 && n_harm == 256 && n_nz == 256 && !a.form.gemm;
   float* nz = a.noise_out ? a.noise_out : w.nzbuf;
   // THE layout of a 256-bin step (round 6): THREE launches on the caller's stream instead of seven on two streams -- exciter and
   // the three tap syntheses (k_front_small, grid.y) | all-pass filter beside the noise filter (grid.y, runs twice as long: half the
@@ -744,7 +744,7 @@ int combsub_rows(const TailCall& a, SynthWs& w, hipStream_t st, void* aux_stream
   // the hardware-queue question of round 5 are gone from this path.
   // Same kernels, same arguments as the layouts below (same bits below 4096 frames: tests/test_small_shapes.py; above, the paired
   // filters' run split differs: rounding-level); knob SMALL_PATH = 1: never; knob STREAM_LAYOUT = 1 / 4: not at batch shapes.
-  if (w.taps3 && fused_shape_ok(R, F, hop, n_ap, n_harm, n_nz, a.fir_impl, true)) {
+  if (w.taps3 && fused_shape_ok(a.form, R, F, hop, n_ap, n_harm, n_nz, a.fir_impl, true)) {
     ExciterJob exc;
     if (make_exciter_job(a.f0_frames, a.initial_phase, B, F, hop, a.sr, a.infer, a.phase0, w.buf0, &exc) != 0) return DDSP_HIP_EHOP;
     TapsJobs jobs;
@@ -758,9 +758,9 @@ int combsub_rows(const TailCall& a, SynthWs& w, hipStream_t st, void* aux_stream
                              n_harm, w.taps3, st, (float)a.sr, &jobs);
     if (ok != 0 || launch_taps_pfa510_batch(jobs, st, &exc) != 0) return DDSP_HIP_ESHAPE;   // exciter + the three tap syntheses
     const FirSecond second{a.noise, a.noise_is_u01, w.taps_nz, nullptr, nz, nullptr, half};
-    if (launch_fir_blk(w.buf0, 0, w.taps, nullptr, w.buf1, nullptr, B, F, hop, 2 * (n_ap - 1), st, a.gen.on ? &a.gen : nullptr, &second) < 0)
+    if (launch_fir_blk(w.buf0, 0, w.taps, nullptr, w.buf1, nullptr, B, F, hop, 2 * (n_ap - 1), st, a.gen.on ? &a.gen : nullptr, &second, 0, Bg) < 0)
       return DDSP_HIP_ESHAPE;
-    if (launch_fir(w.buf1, 0, w.taps3, nz, a.signal, a.harmonic, B, F, hop, 2 * (n_harm - 1), a.fir_impl, st) < 0)
+    if (launch_fir(w.buf1, 0, w.taps3, nz, a.signal, a.harmonic, B, F, hop, 2 * (n_harm - 1), a.fir_impl, st, nullptr, Bg) < 0)
       return DDSP_HIP_ESHAPE;
     return 0;
   }
@@ -781,29 +781,62 @@ int combsub_rows(const TailCall& a, SynthWs& w, hipStream_t st, void* aux_stream
     br.publish(0);
   }
   // noise branch (vocoder.py:854-858)
-  synth_taps(a.c2, a.ld2, nullptr, 0, DDSP_HIP_ACT_EXP, 1.0f / 128.0f, a.t2, DDSP_HIP_MODE_HANN, nullptr, R, n_nz,
+  synth_taps(a.form, a.c2, a.ld2, nullptr, 0, DDSP_HIP_ACT_EXP, 1.0f / 128.0f, a.t2, DDSP_HIP_MODE_HANN, nullptr, R, n_nz,
              w.taps_nz, br.aux);
   const int rn = launch_fir(a.noise, a.noise_is_u01, w.taps_nz, nullptr, nz, nullptr, B, F, hop, 2 * (n_nz - 1), a.fir_impl,
-                            br.aux, &a.gen);
+                            br.aux, &a.gen, Bg);
   // all-pass taps (vocoder.py:843-846; at other bin counts their response lives in buf0 until the exciter overwrites it)
-  synth_allpass_taps(a.c0, a.ld0, a.t0, R, n_ap, w.re, w.im, w.taps, st);
+  synth_allpass_taps(a.form, a.c0, a.ld0, a.t0, R, n_ap, w.re, w.im, w.taps, st);
   if (layout == 4) br.await(0);
   else rc = launch_combtooth(a.f0_frames, a.initial_phase, B, F, hop, a.sr, a.infer, a.phase0, w.buf0, st);
   int r1 = 0;
   if (rc == 0) {
-    r1 = launch_fir(w.buf0, 0, w.taps, nullptr, w.buf1, nullptr, B, F, hop, 2 * (n_ap - 1), a.fir_impl, st);
+    r1 = launch_fir(w.buf0, 0, w.taps, nullptr, w.buf1, nullptr, B, F, hop, 2 * (n_ap - 1), a.fir_impl, st, nullptr, Bg);
     // harmonic magnitude filter with the f0-dependent window (vocoder.py:847-851); half_width_frames = 1.5 sr / (f0 + 1e-3)
     // (:851) is formed in the kernel's epilogue
-    synth_taps(a.c1, a.ld1, nullptr, 0, DDSP_HIP_ACT_EXP, 1.0f, a.t1, DDSP_HIP_MODE_DYNAMIC, a.f0_frames, R, n_harm,
+    synth_taps(a.form, a.c1, a.ld1, nullptr, 0, DDSP_HIP_ACT_EXP, 1.0f, a.t1, DDSP_HIP_MODE_DYNAMIC, a.f0_frames, R, n_harm,
                w.taps, st, (float)a.sr);
   }
   br.join();                                             // always joined, also on the error paths below
   if (rc != 0) return DDSP_HIP_EHOP;
   if (r1 < 0 || rn < 0) return DDSP_HIP_ESHAPE;
   // signal = harmonic + noise (vocoder.py:860): the second harmonic filter adds the branch's result
-  if (launch_fir(w.buf1, 0, w.taps, nz, a.signal, a.harmonic, B, F, hop, 2 * (n_harm - 1), a.fir_impl, st) < 0)
+  if (launch_fir(w.buf1, 0, w.taps, nz, a.signal, a.harmonic, B, F, hop, 2 * (n_harm - 1), a.fir_impl, st, nullptr, Bg) < 0)
     return DDSP_HIP_ESHAPE;
   return 0;
+}
+
+// what ddsp_hip_sins_synth and ddsp_hip_combsub_synth do behind their own argument checks: `rows` over the call, split or not
+int run_tail(const TailCall& call, int n_max, void* ws, size_t ws_bytes, hipStream_t st, void* aux_stream, TailFn rows) {
+  // the stream layout is chosen from "the prime-factor tap synthesis takes these calls", and that kernel stores
+  // 16 bytes at a time: the taps carved out of ws must be 16-byte aligned (ddsp_hip.h states the contract)
+  if ((reinterpret_cast<uintptr_t>(ws) & 15) != 0) return DDSP_HIP_EINVAL;
+  // the uniform draw inside the noise filter (philox.h): the hop-block form's shapes only
+  if (call.gen.on && !(call.hop == 512 && call.n2 <= 257 && (call.fir_impl == 0 || call.fir_impl == 5))) return DDSP_HIP_ESHAPE;
+  const LanePlan plan = lane_plan(call.B, call.F);
+  if (plan.nsub > 1) {
+    const int rc = run_lanes(call, plan, ws, ws_bytes, n_max, st, aux_stream, rows);
+    return rc != 0 ? rc : finish();
+  }
+  Carver c(ws, ws_bytes);
+  SynthWs w;
+  carve_synth(c, call.B, call.F, call.hop, n_max, w);
+  if (!c.ok) return DDSP_HIP_EWS;
+  const int rc = rows(call, w, st, aux_stream);
+  return rc != 0 ? rc : finish();
+}
+
+// the scratch of ddsp_hip_combsub_tail_backward: ONE carve for the size and for the pointers
+struct TailBwdWs { float *d_h1, *dt_h, *dt_ap, *dt_nz, *d_re, *d_im; };
+size_t carve_tail_bwd(Carver& c, int B, int F, int hop, int n_mag, TailBwdWs& w) {
+  const size_t BT = (size_t)B * F * hop, R = (size_t)B * F, N = 2 * (size_t)(n_mag - 1);
+  w.d_h1 = c.take<float>(BT);
+  w.dt_h = c.take<float>(R * N);
+  w.dt_ap = c.take<float>(R * N);
+  w.dt_nz = c.take<float>(R * N);
+  w.d_re = c.take<float>(R * n_mag);
+  w.d_im = c.take<float>(R * n_mag);
+  return align_up(c.used, 256);
 }
 
 }  // namespace
@@ -827,11 +860,10 @@ int ddsp_hip_tail_layout(int combsub, int B, int F, int hop, int n0, int n1, int
   if (!offsets || B <= 0 || F <= 0 || hop <= 0) return DDSP_HIP_EINVAL;
   (void)in_kernel_noise;                                       // (kept in the signature; no layout depends on it)
   for (int i = 0; i < 6; ++i) offsets[i] = -1;
-  const TapsFormScope form;
   int n_max = n1 > n2 ? n1 : n2;
   if (combsub && n0 > n_max) n_max = n0;
   if (lane_plan(B, F).nsub > 1) return 0;                      // sub-batches on lanes: slots are re-used, nothing survives the call
-  if (!fused_shape_ok((long)B * F, F, hop, n0, n1, n2, fir_impl, combsub != 0)) return 0;
+  if (!fused_shape_ok(taps_form(), (long)B * F, F, hop, n0, n1, n2, fir_impl, combsub != 0)) return 0;
   constexpr uintptr_t kBase = 4096;                            // a carve over a pretend base: offsets = pointers - base, null = absent
   Carver c(reinterpret_cast<void*>(kBase), (size_t)1 << 60);
   SynthWs w;
@@ -859,12 +891,8 @@ int ddsp_hip_tail_layout(int combsub, int B, int F, int hop, int n0, int n1, int
 size_t ddsp_hip_combsub_tail_backward_ws_bytes(int B, int F, int hop, int n_mag) {
   if (B <= 0 || F <= 0 || hop <= 0 || n_mag < 2) return 0;
   Carver c(reinterpret_cast<void*>((uintptr_t)4096), (size_t)1 << 60);
-  const size_t BT = (size_t)B * F * hop, R = (size_t)B * F, N = 2 * (size_t)(n_mag - 1);
-  c.take<float>(BT);
-  for (int i = 0; i < 3; ++i) c.take<float>(R * N);
-  c.take<float>(R * n_mag);
-  c.take<float>(R * n_mag);
-  return align_up(c.used, 256);
+  TailBwdWs w;
+  return carve_tail_bwd(c, B, F, hop, n_mag, w);
 }
 
 int ddsp_hip_combsub_tail_backward(const float* f0_frames, const float* c_gd, long ld_gd, const float* c_harm, long ld_harm,
@@ -887,40 +915,36 @@ int ddsp_hip_combsub_tail_backward(const float* f0_frames, const float* c_gd, lo
   const float* taps_h = reinterpret_cast<const float*>(fw + off[3]);
   const float* taps_nz = reinterpret_cast<const float*>(fw + off[4]);
   Carver c(ws, ws_bytes);
-  const size_t BT = (size_t)B * F * hop, R = (size_t)B * F, N = 2 * (size_t)(n_mag - 1);
-  float* d_h1 = c.take<float>(BT);
-  float* dt_h = c.take<float>(R * N);
-  float* dt_ap = c.take<float>(R * N);
-  float* dt_nz = c.take<float>(R * N);
-  float* d_re = c.take<float>(R * n_mag);
-  float* d_im = c.take<float>(R * n_mag);
+  TailBwdWs w;
+  carve_tail_bwd(c, B, F, hop, n_mag, w);
   if (!c.ok) return DDSP_HIP_EWS;
   hipStream_t st = S(stream);
-  const int Ni = (int)N;
+  const long R = (long)B * F;
+  const int Ni = 2 * (n_mag - 1);
   if (g_harm) {
-    if (launch_fir_blk_bwd(h1, 0, taps_h, g_harm, d_h1, dt_h, B, F, hop, Ni, st) != 0) return DDSP_HIP_ESHAPE;
-    const FirBwdSecond second{noise, noise_is_u01, g_noise, dt_nz};
-    if (launch_fir_blk_bwd(comb, 0, taps_ap, d_h1, nullptr, dt_ap, B, F, hop, Ni, st, g_noise ? &second : nullptr) != 0) {
+    if (launch_fir_blk_bwd(h1, 0, taps_h, g_harm, w.d_h1, w.dt_h, B, F, hop, Ni, st) != 0) return DDSP_HIP_ESHAPE;
+    const FirBwdSecond second{noise, noise_is_u01, g_noise, w.dt_nz};
+    if (launch_fir_blk_bwd(comb, 0, taps_ap, w.d_h1, nullptr, w.dt_ap, B, F, hop, Ni, st, g_noise ? &second : nullptr) != 0) {
       // (knob BWD_WPS = 2: the two-wave kernel takes no second job: one launch each)
-      if (launch_fir_blk_bwd(comb, 0, taps_ap, d_h1, nullptr, dt_ap, B, F, hop, Ni, st) != 0) return DDSP_HIP_ESHAPE;
-      if (g_noise && launch_fir_blk_bwd(noise, noise_is_u01, taps_nz, g_noise, nullptr, dt_nz, B, F, hop, Ni, st) != 0) return DDSP_HIP_ESHAPE;
+      if (launch_fir_blk_bwd(comb, 0, taps_ap, w.d_h1, nullptr, w.dt_ap, B, F, hop, Ni, st) != 0) return DDSP_HIP_ESHAPE;
+      if (g_noise && launch_fir_blk_bwd(noise, noise_is_u01, taps_nz, g_noise, nullptr, w.dt_nz, B, F, hop, Ni, st) != 0) return DDSP_HIP_ESHAPE;
     }
   } else if (g_noise) {
-    if (launch_fir_blk_bwd(noise, noise_is_u01, taps_nz, g_noise, nullptr, dt_nz, B, F, hop, Ni, st) != 0) return DDSP_HIP_ESHAPE;
+    if (launch_fir_blk_bwd(noise, noise_is_u01, taps_nz, g_noise, nullptr, w.dt_nz, B, F, hop, Ni, st) != 0) return DDSP_HIP_ESHAPE;
   }
   TapsBwdJobs jobs;
   jobs.n = 0;
   const bool fuse_ap = (reinterpret_cast<uintptr_t>(d_gd) & 15) == 0 && knob(KNOB_AP_BWD_SPLIT) == 0;
   if (g_harm) {
-    jobs.j[jobs.n++] = TapsBwdJob{1, 0, DDSP_HIP_MODE_DYNAMIC, dt_h, c_harm, ld_harm, 1.0f, nullptr, f0_frames, (float)sr, d_harm, nullptr};
+    jobs.j[jobs.n++] = TapsBwdJob{1, 0, DDSP_HIP_MODE_DYNAMIC, w.dt_h, c_harm, ld_harm, 1.0f, nullptr, f0_frames, (float)sr, d_harm, nullptr};
     // the all-pass activation's adjoint rides in that job's last stage (no d re / d im round trip, no fourth launch) when the
     // control gradient can take its 16-byte stores
-    jobs.j[jobs.n++] = fuse_ap ? TapsBwdJob{0, 1, DDSP_HIP_MODE_ROLL, dt_ap, nullptr, 0, 1.0f, nullptr, nullptr, 0.f, d_re, d_im, c_gd, ld_gd, d_gd}
-                               : TapsBwdJob{0, 1, DDSP_HIP_MODE_ROLL, dt_ap, nullptr, 0, 1.0f, nullptr, nullptr, 0.f, d_re, d_im};
+    jobs.j[jobs.n++] = fuse_ap ? TapsBwdJob{0, 1, DDSP_HIP_MODE_ROLL, w.dt_ap, nullptr, 0, 1.0f, nullptr, nullptr, 0.f, w.d_re, w.d_im, c_gd, ld_gd, d_gd}
+                               : TapsBwdJob{0, 1, DDSP_HIP_MODE_ROLL, w.dt_ap, nullptr, 0, 1.0f, nullptr, nullptr, 0.f, w.d_re, w.d_im};
   }
-  if (g_noise) jobs.j[jobs.n++] = TapsBwdJob{1, 0, DDSP_HIP_MODE_HANN, dt_nz, c_nz, ld_nz, 1.0f / 128.0f, nullptr, nullptr, 0.f, d_nz, nullptr};
-  if (jobs.n && launch_taps_pfa510_bwd_jobs(jobs, table, (long)R, st) != 0) return DDSP_HIP_ESHAPE;
-  if (g_harm && !fuse_ap) launch_allpass_backward(c_gd, ld_gd, (long)R, n_mag, d_re, d_im, d_gd, st);
+  if (g_noise) jobs.j[jobs.n++] = TapsBwdJob{1, 0, DDSP_HIP_MODE_HANN, w.dt_nz, c_nz, ld_nz, 1.0f / 128.0f, nullptr, nullptr, 0.f, d_nz, nullptr};
+  if (jobs.n && launch_taps_pfa510_bwd_jobs(jobs, table, R, st) != 0) return DDSP_HIP_ESHAPE;
+  if (g_harm && !fuse_ap) launch_allpass_backward(c_gd, ld_gd, R, n_mag, w.d_re, w.d_im, d_gd, st);
   return finish();
 }
 
@@ -933,17 +957,17 @@ int ddsp_hip_allpass_taps_backward(const float* d_taps, const float* c, long ld,
   if (rows < 0 || n_mag < 2 || ld < n_mag) return DDSP_HIP_EINVAL;
   if (rows == 0) return 0;
   if (!d_taps || !c || !table || !d_c) return DDSP_HIP_EINVAL;
-  const TapsFormScope form;
-  if (n_mag == 256 && !t_taps_gemm && knob(KNOB_AP_BWD_SPLIT) == 0 && (reinterpret_cast<uintptr_t>(d_c) & 15) == 0) {
+  const TapsForm form = taps_form();
+  if (n_mag == 256 && !form.gemm && knob(KNOB_AP_BWD_SPLIT) == 0 && (reinterpret_cast<uintptr_t>(d_c) & 15) == 0) {
     TapsBwdJobs jobs;
     jobs.n = 1;
     jobs.j[0] = TapsBwdJob{0, 1, DDSP_HIP_MODE_ROLL, d_taps, nullptr, 0, 1.0f, nullptr, nullptr, 0.f, nullptr, nullptr, c, ld, d_c};
     if (launch_taps_pfa510_bwd_jobs(jobs, table, rows, S(stream)) == 0) return finish();
   }
   if (!d_re_ws || !d_im_ws) return DDSP_HIP_EWS;
-  const int rc = ddsp_hip_impulse_response_backward(d_taps, nullptr, 0, DDSP_HIP_ACT_NONE, 1.0f, DDSP_HIP_MODE_ROLL, nullptr, rows, n_mag,
-                                                    table, d_re_ws, d_im_ws, stream);
-  if (rc != 0) return rc;
+  synth_taps_bwd(form, d_taps, nullptr, 0, DDSP_HIP_ACT_NONE, 1.0f, table, DDSP_HIP_MODE_ROLL, nullptr, rows, n_mag, d_re_ws, d_im_ws,
+                 S(stream));
+  if (const int rc = finish()) return rc;
   launch_allpass_backward(c, ld, rows, n_mag, d_re_ws, d_im_ws, d_c, S(stream));
   return finish();
 }
@@ -959,29 +983,12 @@ int ddsp_hip_sins_synth(const float* f0_frames, const float* initial_phase, cons
   if (B == 0) return 0;
   if (!f0_frames || !phase0 || !c_amp || !c_gd || !c_nz || !table_ap || !table_nz || !signal)
     return DDSP_HIP_EINVAL;
-  // the stream layout below is chosen from "the prime-factor tap synthesis takes these calls", and that kernel stores
-  // 16 bytes at a time: the taps carved out of ws must be 16-byte aligned (ddsp_hip.h states the contract)
-  if ((reinterpret_cast<uintptr_t>(ws) & 15) != 0) return DDSP_HIP_EINVAL;
   // noise == NULL: the uniform draw happens inside the noise filter (philox.h) from (noise_seed, noise_offset)
   const NoiseGen gen{noise_seed, noise_offset, noise ? 0 : 1, 0u};
-  if (gen.on && !(hop == 512 && n_nz <= 257 && (fir_impl == 0 || fir_impl == 5))) return DDSP_HIP_ESHAPE;
-  const int n_max = n_ap > n_nz ? n_ap : n_nz;
-  hipStream_t st = S(stream);
-  const TapsFormScope form;
   const TailCall call{f0_frames, initial_phase, phase0, c_amp, ld_amp, c_gd, ld_gd, c_nz, ld_nz, noise, noise_is_u01,
                       B, F, hop, sr, infer, H, n_ap, n_nz, nullptr, table_ap, table_nz, signal, harmonic_or_null,
-                      noise_out_or_null, fir_impl, gen};
-  const LanePlan plan = lane_plan(B, F);
-  if (plan.nsub > 1) {
-    const int rc = run_lanes(call, plan, ws, ws_bytes, n_max, st, aux_stream, sins_rows);
-    return rc != 0 ? rc : finish();
-  }
-  Carver c(ws, ws_bytes);
-  SynthWs w;
-  carve_synth(c, B, F, hop, n_max, w);
-  if (!c.ok) return DDSP_HIP_EWS;
-  const int rc = sins_rows(call, w, st, aux_stream);
-  return rc != 0 ? rc : finish();
+                      noise_out_or_null, fir_impl, gen, taps_form(), B};
+  return run_tail(call, n_ap > n_nz ? n_ap : n_nz, ws, ws_bytes, S(stream), aux_stream, sins_rows);
 }
 
 int ddsp_hip_combsub_synth(const float* f0_frames, const float* initial_phase, const double* phase0, const float* c_gd,
@@ -996,27 +1003,13 @@ int ddsp_hip_combsub_synth(const float* f0_frames, const float* initial_phase, c
   if (B == 0) return 0;
   if (!f0_frames || !phase0 || !c_gd || !c_harm || !c_nz || !table_ap || !table_harm || !table_nz || !signal)
     return DDSP_HIP_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(ws) & 15) != 0) return DDSP_HIP_EINVAL;      // as ddsp_hip_sins_synth
   const NoiseGen gen{noise_seed, noise_offset, noise ? 0 : 1, 0u};   // noise == NULL: drawn inside the noise filter (philox.h)
-  if (gen.on && !(hop == 512 && n_nz <= 257 && (fir_impl == 0 || fir_impl == 5))) return DDSP_HIP_ESHAPE;
   int n_max = n_ap > n_nz ? n_ap : n_nz;
   if (n_harm > n_max) n_max = n_harm;
-  hipStream_t st = S(stream);
-  const TapsFormScope form;
   const TailCall call{f0_frames, initial_phase, phase0, c_gd, ld_gd, c_harm, ld_harm, c_nz, ld_nz, noise, noise_is_u01,
                       B, F, hop, sr, infer, n_ap, n_harm, n_nz, table_ap, table_harm, table_nz, signal, harmonic_or_null,
-                      noise_out_or_null, fir_impl, gen};
-  const LanePlan plan = lane_plan(B, F);
-  if (plan.nsub > 1) {
-    const int rc = run_lanes(call, plan, ws, ws_bytes, n_max, st, aux_stream, combsub_rows);
-    return rc != 0 ? rc : finish();
-  }
-  Carver c(ws, ws_bytes);
-  SynthWs w;
-  carve_synth(c, B, F, hop, n_max, w);
-  if (!c.ok) return DDSP_HIP_EWS;
-  const int rc = combsub_rows(call, w, st, aux_stream);
-  return rc != 0 ? rc : finish();
+                      noise_out_or_null, fir_impl, gen, taps_form(), B};
+  return run_tail(call, n_max, ws, ws_bytes, S(stream), aux_stream, combsub_rows);
 }
 
 size_t ddsp_hip_stft_workspace_bytes(int B, int F, int hop) {

@@ -399,13 +399,13 @@ size_t fir_mfma_lds_bytes(int F, int hop, int N, int waves) {
 // 4 = FFT-domain block convolution (fir_fft.hip; hop 512, N <= 512).
 // Returns the implementation used, or <0 when the requested kernel cannot take the shape.
 int launch_fir(const float* x, int x_is_u01, const float* taps, const float* addend, float* out, float* out_plain,
-               int B, int F, int hop, int N, int impl, hipStream_t st, const NoiseGen* noise_gen) {
+               int B, int F, int hop, int N, int impl, hipStream_t st, const NoiseGen* noise_gen, int geometry_batch) {
   const long T = (long)F * hop;
   if (B == 0 || T == 0) return 0;
   if (N & 1) return -1;
   if (noise_gen && noise_gen->on) {                   // only the hop-block form draws its input itself
     if (!(hop == 512 && N <= 512 && (impl == 0 || impl == 5))) return -2;
-    return launch_fir_blk(x, x_is_u01, taps, addend, out, out_plain, B, F, hop, N, st, noise_gen);
+    return launch_fir_blk(x, x_is_u01, taps, addend, out, out_plain, B, F, hop, N, st, noise_gen, nullptr, 0, geometry_batch);
   }
   auto al = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; };
   // the MFMA kernels move float4 / float2: hop % 4 == 0 (so T % 4 == 0), 16-byte aligned signals, 8-byte aligned taps
@@ -417,14 +417,14 @@ int launch_fir(const float* x, int x_is_u01, const float* taps, const float* add
   if (impl == 0 && hop == 512 && N <= 512) {
     // auto: the hop-block form unless it declines the shape (an utterance of 2^28 samples or more: its buffer descriptors
     // span less than 2^30 bytes) -- then the direct forms below, not an error; only an explicit impl = 5 fails there
-    const int r = launch_fir_blk(x, x_is_u01, taps, addend, out, out_plain, B, F, hop, N, st);
+    const int r = launch_fir_blk(x, x_is_u01, taps, addend, out, out_plain, B, F, hop, N, st, nullptr, nullptr, 0, geometry_batch);
     if (r >= 0) return r;
   }
   // 514 .. 1022 taps (n_mag up to 512: the harmonic filter of the classic CombSub configuration): the per-frame 2048-point
   // form in its LONG variant -- the direct form on the matrix pipe costs ~3x as much at these tap counts
   if (impl == 0 && hop == 512 && N > 512 && N <= 1022 && (long)F * hop < (1L << 30)) impl = 4;
-  if (impl == 4) return launch_fir_fft(x, x_is_u01, taps, addend, out, out_plain, B, F, hop, N, st);
-  if (impl == 5) return launch_fir_blk(x, x_is_u01, taps, addend, out, out_plain, B, F, hop, N, st);
+  if (impl == 4) return launch_fir_fft(x, x_is_u01, taps, addend, out, out_plain, B, F, hop, N, st, geometry_batch);
+  if (impl == 5) return launch_fir_blk(x, x_is_u01, taps, addend, out, out_plain, B, F, hop, N, st, nullptr, nullptr, 0, geometry_batch);
   if (impl == 0) impl = fits(8) ? 3 : fits(4) ? 2 : 1;
   if ((impl == 2 && !fits(4)) || (impl == 3 && !fits(8))) return -1;
   if (impl == 2 || impl == 3) {

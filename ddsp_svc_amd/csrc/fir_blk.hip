@@ -375,7 +375,8 @@ int launch_uniform_noise(unsigned long long seed, unsigned long long offset, int
 
 // returns the implementation id (5) or < 0 when the shape is outside this kernel
 int launch_fir_blk(const float* x, int x_is_u01, const float* taps, const float* addend, float* out, float* out_plain,
-                   int B, int F, int hop, int N, hipStream_t st, const NoiseGen* noise_gen, const FirSecond* second, int taps_half) {
+                   int B, int F, int hop, int N, hipStream_t st, const NoiseGen* noise_gen, const FirSecond* second, int taps_half,
+                   int geometry_batch) {
   if (hop != FB_HOP || N < 2 || (N & 1) || N > 512 || (long)F * hop >= (1L << 28)) return -1;   // one utterance stays below 2^30 bytes (buffer descriptors, BufF32::kOutOfRange)
   FirBlkGeom g;
   g.F = F; g.N = N; g.T = F * hop;
@@ -383,20 +384,16 @@ int launch_fir_blk(const float* x, int x_is_u01, const float* taps, const float*
   // run length: as many workgroups as the chip holds at once (three waves per SIMD, 2 waves each: six per CU), one round,
   // equal work; every run but an utterance's first pays one warm-up block (three transforms; a pair costs four)
   const long slots = 3L * 2 * 256;
-  const int Bg = t_geometry_batch > 0 ? t_geometry_batch : B;          // kernels.h: a sub-batch keeps the whole call's split
-  long per_utt = slots / (Bg > 0 ? Bg : 1);
+  const int Bg = geometry_batch > 0 ? geometry_batch : B;              // kernels.h: a sub-batch keeps the whole call's split
+  const bool batch_shape = (long)Bg * F >= kSmallRows;
   // two jobs share the one round of resident workgroups: runs twice as long, half the warm-up passes (at streaming shapes every
   // workgroup is resident anyway and the split stays what the one-job launches of the same shape use: same bits)
-  if (second && !second->seq && (long)Bg * F >= kSmallRows) per_utt = slots / (2 * (Bg > 0 ? Bg : 1));
-  if (per_utt < 1) per_utt = 1;
-  int run = (int)((g.pairs + per_utt - 1) / per_utt);
+  const int sharers = second && !second->seq && batch_shape ? 2 : 1;
   // at least three pairs per workgroup (each pays a warm-up block and its twiddles) -- except at streaming shapes, where every
   // workgroup is resident at once anyway and the launch is as long as its longest workgroup: one pair each
-  if (run < 3 && (long)Bg * F >= kSmallRows) run = 3;
-  if (const long v = knob(KNOB_BLK_RUN)) { if (v >= 1) run = (int)v; }
-  if (run > g.pairs) run = g.pairs;
-  g.run = run;
-  g.runs_per_utt = (g.pairs + run - 1) / run;
+  const RunSplit rs = run_split(g.pairs, slots, Bg, sharers, batch_shape ? 3 : 1, knob(KNOB_BLK_RUN));
+  g.run = rs.run;
+  g.runs_per_utt = rs.runs_per_utt;
   g.turns = knob(KNOB_BLK_TURNS) == 1 ? 0 : 1;
   const long wgs = (long)B * g.runs_per_utt;
   if (wgs > 0x7fffffffL) return -1;

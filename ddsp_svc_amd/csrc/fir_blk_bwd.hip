@@ -525,25 +525,16 @@ int launch_fir_blk_bwd(const float* x, int x_is_u01, const float* taps, const fl
   g.F = F; g.N = N; g.T = F * hop;
   g.pairs = (F + 1) / 2;
   const long slots = 4L * 256;                                  // 2 waves per SIMD, two waves per workgroup
-  long per_utt = slots / (B > 0 ? B : 1);
-  if (per_utt < 1) per_utt = 1;
-  int run = (int)((g.pairs + per_utt - 1) / per_utt);
-  if (run < 3) run = 3;
-  if (const long v = knob(KNOB_BLK_RUN)) { if (v >= 1) run = (int)v; }
-  if (run > g.pairs) run = g.pairs;
-  g.run = run;
-  g.runs_per_utt = (g.pairs + run - 1) / run;
+  const RunSplit rs = run_split(g.pairs, slots, B, 1, 3, knob(KNOB_BLK_RUN));
+  g.run = rs.run;
+  g.runs_per_utt = rs.runs_per_utt;
   if (second && (d_x || knob(KNOB_BWD_WPS) == 2)) return -1;    // a second job rides in the three-wave tap-gradient kernel only
   if (!d_x && knob(KNOB_BWD_WPS) != 2) {                         // the tap gradient alone: three waves per SIMD, six workgroups per CU
     const long slots6 = 6L * 256;
-    long pu = slots6 / ((second ? 2L : 1L) * (B > 0 ? B : 1));    // two jobs share the one round: runs twice as long, half the warm-ups
-    if (pu < 1) pu = 1;
-    int run6 = (int)((g.pairs + pu - 1) / pu);
-    if (run6 < 3) run6 = 3;
-    if (const long v = knob(KNOB_BLK_RUN)) { if (v >= 1) run6 = (int)v; }
-    if (run6 > g.pairs) run6 = g.pairs;
-    g.run = run6;
-    g.runs_per_utt = (g.pairs + run6 - 1) / run6;
+    // two jobs share the one round: runs twice as long, half the warm-ups
+    const RunSplit rs6 = run_split(g.pairs, slots6, B, second ? 2 : 1, 3, knob(KNOB_BLK_RUN));
+    g.run = rs6.run;
+    g.runs_per_utt = rs6.runs_per_utt;
     const long wgs6 = (long)B * g.runs_per_utt;
     if (wgs6 > 0x7fffffffL) return -1;
     FirBwdJobs jobs;

@@ -209,7 +209,7 @@ __global__ void __launch_bounds__(fft::THREADS, LONG ? 3 : 4) k_fir_fft(const fl
 
 // returns the implementation id (4) or < 0 when the shape is outside this kernel
 int launch_fir_fft(const float* x, int x_is_u01, const float* taps, const float* addend, float* out, float* out_plain,
-                   int B, int F, int hop, int N, hipStream_t st) {
+                   int B, int F, int hop, int N, hipStream_t st, int geometry_batch) {
   if (hop != FF_HOP || N < 2 || (N & 1) || N > 1022 || (long)F * hop >= (1L << 30)) return -1;
   FirFftGeom g;
   g.F = F; g.N = N; g.T = F * hop;
@@ -217,15 +217,10 @@ int launch_fir_fft(const float* x, int x_is_u01, const float* taps, const float*
   // run length (own pairs per workgroup): as many workgroups as the chip holds at once (3 per CU at this
   // kernel's LDS budget), so all of them run in one round with equal work; every run pays two warm-up pairs
   const long slots = 3 * 256;
-  const int Bg = t_geometry_batch > 0 ? t_geometry_batch : B;          // kernels.h: a sub-batch keeps the whole call's split
-  long per_utt = slots / (Bg > 0 ? Bg : 1);
-  if (per_utt < 1) per_utt = 1;
-  int run = (int)((g.pairs + per_utt - 1) / per_utt);
-  if (run < 3) run = 3;
-  if (const long v = knob(KNOB_FFT_RUN)) { if (v >= 1) run = (int)v; }
-  if (run > g.pairs) run = g.pairs;
-  g.run = run;
-  g.runs_per_utt = (g.pairs + run - 1) / run;
+  const int Bg = geometry_batch > 0 ? geometry_batch : B;              // kernels.h: a sub-batch keeps the whole call's split
+  const RunSplit rs = run_split(g.pairs, slots, Bg, 1, 3, knob(KNOB_FFT_RUN));
+  g.run = rs.run;
+  g.runs_per_utt = rs.runs_per_utt;
   const long wgs = (long)B * g.runs_per_utt;
   if (wgs > 0x7fffffffL) return -1;
   hipLaunchKernelGGL(k_fir_fft<true>, dim3((unsigned)wgs), dim3(fft::THREADS), 0, st, x, x_is_u01, taps, addend, out, out_plain, g);

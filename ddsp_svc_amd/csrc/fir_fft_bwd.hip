@@ -220,15 +220,9 @@ int launch_fir_fft_bwd(const float* x, int x_is_u01, const float* taps, const fl
   // run length: one round of resident workgroups (two per CU at this kernel's register budget), equal work; every run but an
   // utterance's first pays two of a pair's five transforms for its carry
   const long slots = DDSP_FFB_WGS * 256;
-  const int Bg = t_geometry_batch > 0 ? t_geometry_batch : B;
-  long per_utt = slots / (Bg > 0 ? Bg : 1);
-  if (per_utt < 1) per_utt = 1;
-  int run = (int)((g.pairs + per_utt - 1) / per_utt);
-  if (run < 3) run = 3;
-  if (const long v = knob(KNOB_FFT_RUN)) { if (v >= 1) run = (int)v; }
-  if (run > g.pairs) run = g.pairs;
-  g.run = run;
-  g.runs_per_utt = (g.pairs + run - 1) / run;
+  const RunSplit rs = run_split(g.pairs, slots, B, 1, 3, knob(KNOB_FFT_RUN));
+  g.run = rs.run;
+  g.runs_per_utt = rs.runs_per_utt;
   const long wgs = (long)B * g.runs_per_utt;
   if (wgs > 0x7fffffffL) return -1;
   // the held last row takes two atomic adds per tap (frames F - 1 and F)

@@ -4,13 +4,9 @@
 #include <stddef.h>
 #include "ddsp_common.h"
 #include "tuning.h"
+#include "run_split.h"
 
 namespace ddsp {
-// Batch size the filters choose their run length from.  A run's first tap spectrum comes out of a differently packed transform,
-// so the LAST BITS of a filter's output depend on how an utterance's block pairs are split into runs, and that split follows B
-// (one round of resident workgroups).  A sub-batch of a split call (api.hip, lanes) sets this to the WHOLE call's B, so that
-// its samples are those of the unsplit call bit for bit; 0 = the launch's own B.
-extern thread_local int t_geometry_batch;
 int spl_for_hop(int hop);
 void launch_upsample(const float* sig, int B, int F, int C, int hop, float* out, hipStream_t st);
 void launch_remove_above_fmax(const float* amps, const float* pitch, long rows, int H, float fmax, int level_start,
@@ -93,11 +89,13 @@ void launch_allpass_backward(const float* c, long ld, long rows, int n, const fl
 size_t fir_mfma_lds_bytes(int F, int hop, int N, int waves);
 struct NoiseGen;   // philox.h: (seed, offset) of the in-kernel uniform draw
 // noise_gen != null && on: the input signal is drawn inside the kernel (hop 512, N <= 512 only: -2 otherwise)
+// geometry_batch (here, launch_fir_blk, launch_fir_fft): the batch the run split follows (run_split.h) -- a sub-batch of a split
+// call passes the WHOLE call's B; 0 = the launch's own B
 int launch_fir(const float* x, int x_is_u01, const float* taps, const float* addend, float* out, float* out_plain,
-               int B, int F, int hop, int N, int impl, hipStream_t st, const NoiseGen* noise_gen = nullptr);
+               int B, int F, int hop, int N, int impl, hipStream_t st, const NoiseGen* noise_gen = nullptr, int geometry_batch = 0);
 int launch_uniform_noise(unsigned long long seed, unsigned long long offset, int B, long T, float* out, hipStream_t st);
 int launch_fir_fft(const float* x, int x_is_u01, const float* taps, const float* addend, float* out, float* out_plain,
-                   int B, int F, int hop, int N, hipStream_t st);
+                   int B, int F, int hop, int N, hipStream_t st, int geometry_batch = 0);
 // second != null: a second, independent filter of the same shape (B, F, hop, N) rides in the same launch (k_fir_blk6, grid.y);
 // -1 when this launch cannot take it (the in-kernel noise draw, the two-wave kernel)
 // taps_half: the tap rows are the first N/2 + 1 taps of an EVEN response (a zero-phase magnitude filter's under the Hann window:
@@ -108,7 +106,7 @@ int launch_fir_fft(const float* x, int x_is_u01, const float* taps, const float*
 struct FirSecond { const float* x; int x_is_u01; const float* taps; const float* addend; float* out; float* out_plain; int taps_half; int seq = 0; };
 int launch_fir_blk(const float* x, int x_is_u01, const float* taps, const float* addend, float* out, float* out_plain,
                    int B, int F, int hop, int N, hipStream_t st, const NoiseGen* noise_gen = nullptr,
-                   const FirSecond* second = nullptr, int taps_half = 0);
+                   const FirSecond* second = nullptr, int taps_half = 0, int geometry_batch = 0);
 // second != null: a second, independent TAP gradient of the same shape rides in the same launch (k_fir_blk_bwd6, grid.y); -1 when
 // this launch cannot take it (an input gradient is wanted, knob BWD_WPS = 2)
 struct FirBwdSecond { const float* x; int x_is_u01; const float* grad_out; float* d_taps; };

@@ -222,14 +222,9 @@ int launch_mel(const float* audio, int B, int T, const float* window, int n_fft,
   int wps = 3;
   if (const long v = knob(KNOB_MEL_WPS)) { if (v >= 1) wps = (int)v; }
   const long slots = (long)wps * 256;
-  long per_utt = slots / (B > 0 ? B : 1);
-  if (per_utt < 1) per_utt = 1;
-  int run = (int)((g.pairs + per_utt - 1) / per_utt);
-  if (run < 4) run = 4;
-  if (const long v = knob(KNOB_MEL_RUN)) { if (v >= 1) run = (int)v; }
-  if (run > g.pairs) run = g.pairs;
-  g.run = run;
-  g.runs_per_utt = (g.pairs + run - 1) / run;
+  const RunSplit rs = run_split(g.pairs, slots, B, 1, 4, knob(KNOB_MEL_RUN));
+  g.run = rs.run;
+  g.runs_per_utt = rs.runs_per_utt;
   const long wgs = (long)B * g.runs_per_utt;
   if (wgs > 0x7fffffffL) return -1;
   if (wps >= 4)
@@ -505,14 +500,9 @@ int launch_mel_bwd(const float* audio, int B, int T, const float* window, int n_
   int wps = 3;
   if (const long v = knob(KNOB_MEL_WPS)) { if (v >= 1) wps = v >= 3 ? 3 : 2; }
   const long slots = (long)wps * 256;
-  long per_utt = slots / B;
-  if (per_utt < 1) per_utt = 1;
-  int run = (int)((g.pairs + per_utt - 1) / per_utt);
-  if (run < 4) run = 4;
-  if (const long v = knob(KNOB_MEL_RUN)) { if (v >= 1) run = (int)v; }
-  if (run > g.pairs) run = g.pairs;
-  g.run = run;
-  g.runs_per_utt = (g.pairs + run - 1) / run;
+  const RunSplit rs = run_split(g.pairs, slots, B, 1, 4, knob(KNOB_MEL_RUN));
+  g.run = rs.run;
+  g.runs_per_utt = rs.runs_per_utt;
   const long wgs = (long)B * g.runs_per_utt;
   if (wgs > 0x7fffffffL) return -1;
   if (wps == 3)

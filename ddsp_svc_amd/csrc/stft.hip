@@ -759,18 +759,14 @@ int launch_stft_filter(const float* exc, const float* noise, int noise_is_u01, c
   // run length: as many workgroups as the chip holds at once, so all of them run in one round with equal work (a
   // partial second round costs more than the longer runs; every run pays its warm-up)
   const long slots = (long)wg_per_cu * 256;
-  long per_utt = slots / (B > 0 ? B : 1);
-  if (per_utt < 1) per_utt = 1;
-  int run = (int)((g.pairs + per_utt - 1) / per_utt);
   // at least three times the warm-up per workgroup -- except at streaming shapes (gui.py:118-133: B = 1, a fraction of a second),
   // where every workgroup is resident at once anyway and the launch is as long as its longest workgroup: one pair each (round 6;
   // six pairs + two of warm-up were 19 us of a 57 us step there).  The overlap-add order per sample does not depend on the
   // split (a run's warm-up pairs rebuild the ring in frame order): same bits, tests/test_small_shapes.py; knob SMALL_PATH = 1: off
-  if (run < 3 * warm && ((long)B * F >= kSmallRows || knob(KNOB_SMALL_PATH) == 1)) run = 3 * warm;
-  if (const long v = knob(KNOB_STFT_RUN)) { if (v >= 1) run = (int)v; }
-  if (run > g.pairs) run = g.pairs;
-  g.run = run;
-  g.runs_per_utt = (g.pairs + run - 1) / run;
+  const int min_run = ((long)B * F >= kSmallRows || knob(KNOB_SMALL_PATH) == 1) ? 3 * warm : 1;
+  const RunSplit rs = run_split(g.pairs, slots, B, 1, min_run, knob(KNOB_STFT_RUN));
+  g.run = rs.run;
+  g.runs_per_utt = rs.runs_per_utt;
   const long wgs = (long)B * g.runs_per_utt;
   if (wgs > 0x7fffffffL) return -1;
 #define DDSP_STFT_LAUNCH(R_, WPS_)                                                                                  \
@@ -811,14 +807,9 @@ int launch_stft_filter_bwd(const float* exc, const float* noise, int noise_is_u0
   if (win == 2048) { if (const long v = knob(KNOB_STFT_WPS)) { if (v == 2 || v == 3) wps = (int)v; } }
   const int wg_per_cu = win == 2048 ? wps : 4;
   const long slots = (long)wg_per_cu * 256;
-  long per_utt = slots / (B > 0 ? B : 1);
-  if (per_utt < 1) per_utt = 1;
-  int run = (int)((g.pairs + per_utt - 1) / per_utt);
-  if (run < 2) run = 2;
-  if (const long v = knob(KNOB_STFT_RUN)) { if (v >= 1) run = (int)v; }
-  if (run > g.pairs) run = g.pairs;
-  g.run = run;
-  g.runs_per_utt = (g.pairs + run - 1) / run;
+  const RunSplit rs = run_split(g.pairs, slots, B, 1, 2, knob(KNOB_STFT_RUN));
+  g.run = rs.run;
+  g.runs_per_utt = rs.runs_per_utt;
   const long wgs = (long)B * g.runs_per_utt;
   if (wgs > 0x7fffffffL) return -1;
   if (win == 2048 && wps == 3)
