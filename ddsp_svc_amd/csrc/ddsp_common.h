@@ -103,7 +103,7 @@ struct PhaseCfg {
   int has_ip;
   // f0.double() / sr as a product with the correctly rounded reciprocal plus one fma-residual correction
   // (Markstein): q0 = a r, e = a - q0 sr (exact in fma), q = q0 + e r -- the correctly rounded quotient (checked
-  // exhaustively against IEEE division over 1.5 M float32 f0 values for the common sampling rates) at 3 float64
+  // against IEEE division over 1.5 M float32 f0 values at each common sampling rate, tests/test_device_units.py) at 3 float64
   // operations instead of the ~15 of the hardware division sequence.
   __device__ __forceinline__ double term(float f0u) const {
     if (!infer) return (double)div_pos(f0u, sr_f);               // float32 terms (vocoder.py:568); f0u >= 0, sr_f a normal positive
@@ -237,8 +237,10 @@ __device__ __forceinline__ float tanh_hw(float x) {
 }
 
 // exp(x) on the hardware base-2 exponential: x log2(e) is split into its float32 rounding t and the residual r (two-constant
-// log2(e)), exp2(t) (1 + r ln 2).  Relative error ~1e-7 for |x| <= 80 (a bare exp2(x * log2e) is off by |x| * 6e-8); 3 fma / mul +
-// v_exp_f32 + 2 fma against the ~24 instructions of expf.  The control activations exp(c) of every module (vocoder.py:580, :603,
+// log2(e)), exp2(t) (1 + r ln 2).  Relative error <= 1.5 * 2^-23 = 1.8e-7 for |x| <= 80: v_exp_f32 is good to 1 ulp (2^-23), the last
+// fma rounds once more (2^-24), and the residual's own error is below 1e-11; measured against float64 on MI355X: 1.36e-7 = 1.14 * 2^-23
+// over 2^20 arguments (tests/test_device_units.py; a bare exp2(x * log2e) is off by |x| * 6e-8).  3 fma / mul + v_exp_f32 + 2 fma
+// against the ~24 instructions of expf.  The control activations exp(c) of every module (vocoder.py:580, :603,
 // :835-836, :661-664) go through it.
 __device__ __forceinline__ float exp_hw(float x) {
   const float l2e_hi = 1.44269502f;                  // fl32(log2 e)
@@ -275,8 +277,8 @@ __device__ __forceinline__ float sinc_f32(float z) {
 // sin(a) for |a| up to a few thousand radians (the sinusoid bank reaches 256*pi).  The argument is brought to
 // [-0.5, 0.5] revolutions with a two-constant split of 1/(2 pi) -- fma(a, hi, -n) is exact up to one rounding at
 // magnitude 0.5 -- and handed to the hardware sine, which takes revolutions (v_sin_f32).  Against float64 on
-// MI355X: max abs error 3.9e-7, rms 7.5e-8 over |a| <= 805 (profiles/r01_v3_sin_probe.log; ocml sinf: 7e-8 / 1.8e-8
-// at 3.4x the cost).  4 VALU + 1 transcendental.
+// MI355X: max abs error <= 3.9e-7, rms 7.5e-8 over |a| <= 805 (held by tests/test_device_units.py, which measures 3.2e-7 over 2^20
+// arguments; ocml sinf: 7e-8 / 1.8e-8 at 3.4x the cost).  4 VALU + 1 transcendental.
 __device__ __forceinline__ float sin_turns(float a) {
   const float inv_hi = 0.15915494f;                  // fl32(1/(2 pi)) = 0x3E22F983
   const float inv_lo = 6.4206383e-9f;                // 1/(2 pi) - inv_hi
