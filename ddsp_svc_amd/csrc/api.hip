@@ -8,6 +8,7 @@
 #include "frame_features.h"
 #include "resblock.h"
 #include "generator_tail.h"
+#include "conformer_conv.h"
 #include <atomic>
 #include <stdio.h>
 #include <mutex>
@@ -1500,6 +1501,33 @@ int ddsp_hip_output_head(const float* x, const float* w, const float* bias, floa
   if (!x || !w || !bias || !y || x == y) return DDSP_HIP_EINVAL;
   if (reinterpret_cast<uintptr_t>(y) & 3) return DDSP_HIP_EINVAL;
   launch_output_head(x, w, bias, slope, y, B, C, T, S(stream));
+  return finish();
+}
+
+int ddsp_hip_conformer_conv_tile(int D) { return cconv::shape_ok(D) ? cconv::kTT : 0; }
+
+size_t ddsp_hip_conformer_conv_pack_bytes(int D, int norm) { return conformer_conv_pack_bytes(D, norm); }
+
+int ddsp_hip_conformer_conv_pack(const float* w1, const float* b1, const float* wd, const float* bd, const float* w2, const float* b2,
+                                 const float* gamma, const float* beta, int D, void* packed, size_t packed_bytes) {
+  if (!w1 || !b1 || !wd || !bd || !w2 || !b2 || !packed || (gamma == nullptr) != (beta == nullptr)) return DDSP_HIP_EINVAL;
+  const size_t need = conformer_conv_pack_bytes(D, gamma != nullptr);
+  if (need == 0) return DDSP_HIP_ESHAPE;
+  if (packed_bytes < need) return DDSP_HIP_EWS;
+  conformer_conv_pack(w1, b1, wd, bd, w2, b2, gamma, beta, D, static_cast<float*>(packed));
+  return 0;
+}
+
+int ddsp_hip_conformer_conv(const float* x, float* y, const void* packed, size_t packed_bytes, int B, long L, int D, int norm,
+                            float eps, int add_input, void* stream) {
+  if (B < 0 || L < 1 || !(eps == eps) || eps - eps != 0.f) return DDSP_HIP_EINVAL;
+  if (!cconv::shape_ok(D) || L > (1L << 40)) return DDSP_HIP_ESHAPE;
+  if (B == 0) return 0;
+  if (!x || !y || !packed || x == y) return DDSP_HIP_EINVAL;
+  if (packed_bytes < conformer_conv_pack_bytes(D, norm)) return DDSP_HIP_EWS;
+  if ((reinterpret_cast<uintptr_t>(packed) & 3) || (reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(y) & 15))
+    return DDSP_HIP_EINVAL;                            // the kernel reads and writes 4 channels at a time
+  launch_conformer_conv(x, y, static_cast<const float*>(packed), B, L, D, norm ? 1 : 0, eps, add_input ? 1 : 0, S(stream));
   return finish();
 }
 

@@ -14,7 +14,7 @@
  *     T = F*hop; control tensors take a row stride `ld` (floats between consecutive frames) so
  *     the torch.split views of Unit2Control's output can be passed without a copy;
  *   - more than 65 535 utterances in one call (a grid's limit in y and z): ddsp_hip_resblock1, ddsp_hip_upsample_stage,
- *     ddsp_hip_output_head, ddsp_hip_resample and ddsp_hip_mel_shifted_spectrogram split the batch into launches of 65 535; ddsp_hip_fast_source and
+ *     ddsp_hip_output_head, ddsp_hip_conformer_conv, ddsp_hip_resample and ddsp_hip_mel_shifted_spectrogram split the batch into launches of 65 535; ddsp_hip_fast_source and
  *     ddsp_hip_combsubsuperfast_synth run their exciter on a flat grid then; ddsp_hip_sine_source(_drawn),
  *     ddsp_hip_spectral_loss(_backward), ddsp_hip_stft_loss(_backward), ddsp_hip_mel_spectrogram_backward,
  *     ddsp_hip_sola_splice, ddsp_hip_volume, ddsp_hip_gate, ddsp_hip_pool1d, ddsp_hip_fft_convolve with
@@ -580,6 +580,28 @@ int ddsp_hip_upsample_stage(const float* x, const float* src, float* y, const vo
 int ddsp_hip_output_head_tile(int C);
 int ddsp_hip_output_head(const float* x, const float* w, const float* bias, float slope, float* y, int B, int C, long T,
                          void* stream);
+
+/* The conformer conv module of Unit2Control's decoder and of every PCmer layer (diffusion/model_conformer_naive.py:117-150, the
+ * same text in reflow/, ddsp/pcmer.py:189-216), csrc/conformer_conv.h.  As above, these entry points came after version 165
+ * without a version step.
+ *   net(x) = Conv1d(2 D, D, 1)(silu(Conv1d(2 D, 2 D, 31, padding 15, groups 2 D)(glu(Conv1d(D, 4 D, 1)(ln(x))))))
+ * over x [B, L, D] contiguous (the module's own layout: no transposed copy), ln an optional LayerNorm(D) with the given eps, glu
+ * = rows [0, 2 D) times the sigmoid of rows [2 D, 4 D), the depthwise convolution a cross-correlation that zero-pads the GLU's
+ * output.  D = 256 (DDSP_HIP_ESHAPE otherwise), float32, forward only.
+ * ddsp_hip_conformer_conv_tile: output frames per workgroup (98); 0 for a D the kernel does not take.
+ * ddsp_hip_conformer_conv_pack_bytes / _pack: HOST weights w1 [4 D][D], b1 [4 D], wd [2 D][31], bd [2 D], w2 [D][2 D], b2 [D] and
+ * gamma, beta [D] (both null: no LayerNorm) -> the table the kernel reads, written to HOST memory (the caller copies it to the
+ * device once and keeps it).  0 bytes / DDSP_HIP_ESHAPE out of range, DDSP_HIP_EWS short.
+ * ddsp_hip_conformer_conv: y = net(x), or x + net(x) with add_input (the un-normalised x); norm != 0 needs a table packed with
+ * gamma and beta (DDSP_HIP_EWS otherwise).  1 <= L <= 2^40 (DDSP_HIP_EINVAL / DDSP_HIP_ESHAPE); x and y 16-byte aligned; x must
+ * not be y (a tile reads its neighbours' frames: DDSP_HIP_EINVAL); B = 0 is a no-op.  One launch (per 65 535 utterances), f32
+ * MFMA, 150.5 KB of LDS per workgroup.  No workspace, no allocation, no synchronisation. */
+int ddsp_hip_conformer_conv_tile(int D);
+size_t ddsp_hip_conformer_conv_pack_bytes(int D, int norm);
+int ddsp_hip_conformer_conv_pack(const float* w1, const float* b1, const float* wd, const float* bd, const float* w2, const float* b2,
+                                 const float* gamma, const float* beta, int D, void* packed, size_t packed_bytes);
+int ddsp_hip_conformer_conv(const float* x, float* y, const void* packed, size_t packed_bytes, int B, long L, int D, int norm,
+                            float eps, int add_input, void* stream);
 
 #ifdef __cplusplus
 }
