@@ -1,0 +1,53 @@
+"""Park, swap, undo: how every ``patch_reference_*`` puts a dispatcher in the place of one of the reference's own names.  The
+original is parked next to it as ``_reference_<name>``, once; the swap is the caller's; the undo binds the original back."""
+import sys
+
+
+def park(owner, name):
+    """Store ``owner.<name>`` (``owner``: a module or a class) as ``owner._reference_<name>`` unless ``owner`` itself holds one
+    already -- a subclass that inherits a parked attribute parks its own -- and return the parked original."""
+    if "_reference_" + name not in vars(owner):
+        setattr(owner, "_reference_" + name, getattr(owner, name))
+    return getattr(owner, "_reference_" + name)
+
+
+def unpark(owner, name):
+    """Bind the parked original back as ``owner.<name>`` and drop the parked attribute; nothing when it was never parked."""
+    if "_reference_" + name in vars(owner):
+        setattr(owner, name, getattr(owner, "_reference_" + name))
+        delattr(owner, "_reference_" + name)
+
+
+def rebind_everywhere(mapping, skip=()):
+    """Every module that bound one of ``mapping``'s keys by name (``from ddsp.core import upsample`` in flask_api.py:12,
+    gui_diff.py:10, main_reflow.py:13, ...; ``from ddsp.vocoder import CombSubFast`` in diffusion/vocoder.py:13) gets the value
+    instead -- found by IDENTITY over ``sys.modules``, so no list of importers has to be kept up to date.  Attributes whose name
+    starts with ``_reference_`` (where the originals are parked) and the modules in ``skip`` are left alone.  Returns the
+    bindings it changed as ``(module, name, old value, new value)`` -- ``undo_rebound`` undoes exactly those."""
+    ids = {id(k): v for k, v in mapping.items()}
+    changed = []
+    for mod in list(sys.modules.values()):
+        if mod is None or mod in skip:
+            continue
+        try:
+            items = list(vars(mod).items())
+        except TypeError:                                # a module-like object without a __dict__
+            continue
+        for name, val in items:
+            new = ids.get(id(val))
+            if new is not None and not name.startswith("_reference_"):
+                try:
+                    setattr(mod, name, new)
+                    changed.append((mod, name, val, new))
+                except Exception:                        # noqa: BLE001  (read-only module objects)
+                    pass
+    return changed
+
+
+def undo_rebound(changed):
+    """Empty ``changed`` (what ``rebind_everywhere`` returned): each binding goes back to its old value where it is still the
+    new one; a binding that somebody else changed since is left as it is."""
+    while changed:
+        mod, name, old, new = changed.pop()
+        if getattr(mod, name, None) is new:
+            setattr(mod, name, old)

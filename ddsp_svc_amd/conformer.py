@@ -19,7 +19,8 @@ B L below which the same-GPU torch chain was measured faster (tools/conformer_be
 import torch
 
 from . import _ffi
-from . import nsf_generator as _ng
+from ._modules import needs_grad, on_device, packed_table, pad_of, plain, torch_faster
+from ._patching import park, unpark
 
 DIMS = (256,)
 TAPS = 31
@@ -37,31 +38,19 @@ def tile(D):
     return int(_ffi.lib().ddsp_hip_conformer_conv_tile(int(D)))
 
 
-def _packed(weights, norm, D, device):
-    """the kernel's weight table on ``device``, in ``nsf_generator``'s cache and under its bound: packed on the host once per set
-    of tensors, found again by their ``data_ptr`` and rebuilt when one of them was written in place (``_version``)"""
-    flat = list(weights) + (list(norm) if norm is not None else [])
-    key = (str(device), "conformer", D, norm is not None) + tuple(t.data_ptr() for t in flat)
-    versions = tuple(t._version for t in flat)
-    hit = _ng._PACKED.get(key)
-    if hit is not None and hit[0] == versions:
-        return hit[1]
-    lib = _ffi.lib()
-    with torch.no_grad():
-        host = [t.detach().to("cpu", torch.float32).contiguous() for t in flat]
-    nbytes = int(lib.ddsp_hip_conformer_conv_pack_bytes(D, 1 if norm is not None else 0))
+def _pack(dims, flat):
+    """the host table of ``(w1, b1, wd, bd, w2, b2)`` and, with ``dims = (D, True)``, ``(gamma, beta)``, for ``packed_table``"""
+    (D, normed), lib = dims, _ffi.lib()
+    nbytes = int(lib.ddsp_hip_conformer_conv_pack_bytes(D, int(normed)))
     if nbytes == 0:
         raise ValueError("conv_module: D = %d is outside the kernel's range" % D)
-    table = torch.empty(nbytes // 4, dtype=torch.float32)
-    ptrs = [t.data_ptr() for t in host] + ([None, None] if norm is None else [])
-    _ffi.check(lib.ddsp_hip_conformer_conv_pack(*ptrs, D, table.data_ptr(), nbytes))
-    table = table.to(device)
+    with torch.no_grad():
+        staged = [t.detach().to("cpu", torch.float32).contiguous() for t in flat]
+    host = torch.empty(nbytes // 4, dtype=torch.float32)
+    ptrs = [t.data_ptr() for t in staged] + ([] if normed else [None, None])
+    _ffi.check(lib.ddsp_hip_conformer_conv_pack(*ptrs, D, host.data_ptr(), nbytes))
     PACKS["count"] += 1
-    with _ng._LOCK:
-        while len(_ng._PACKED) >= _ng._PACKED_MAX:
-            _ng._PACKED.pop(next(iter(_ng._PACKED)))
-        _ng._PACKED[key] = (versions, table, flat)     # the tensors stay alive, so a data_ptr cannot come back as another's
-    return table
+    return host
 
 
 def _check_weights(weights, norm, D):
@@ -97,7 +86,8 @@ def conv_module(x, weights, norm=None, eps=1e-5, add_input=False, out=None):
         raise ValueError("conv_module: out must be a contiguous float32 tensor of x's shape")
     if B == 0:
         return y
-    table = _packed(weights, norm, D, x.device)
+    flat = list(weights) + (list(norm) if norm is not None else [])
+    table = packed_table("conformer", (D, norm is not None), flat, x.device, _pack)
     CALLS["hip"] += 1
     _ffi.check(_ffi.lib().ddsp_hip_conformer_conv(x.data_ptr(), y.data_ptr(), table.data_ptr(), table.numel() * 4, B, L, D,
                                                   0 if norm is None else 1, float(eps), 1 if add_input else 0,
@@ -126,32 +116,27 @@ def encoder(x, layers, out=None):
 # ---- the reference's modules --------------------------------------------------------------------------------------------------
 
 def _plain(c):
-    """a module whose ``weight`` and ``bias`` are plain float32 parameters and that carries no hook (a weight-norm hook recomputes
-    ``weight``; any other expects the module's own forward to run)"""
-    if not isinstance(c._parameters.get("weight"), torch.Tensor) or not isinstance(c._parameters.get("bias"), torch.Tensor):
-        return False
-    if c._forward_pre_hooks or c._forward_hooks:
-        return False
-    return c.weight.dtype == torch.float32 and c.bias.dtype == torch.float32
+    """``_modules.plain`` and a bias that is a plain float32 parameter too"""
+    return plain(c) and isinstance(c._parameters.get("bias"), torch.Tensor) and c.bias.dtype == torch.float32
 
 
 def _pointwise(c, cin, cout):
     return (isinstance(c, torch.nn.Conv1d) and _plain(c) and c.in_channels == cin and c.out_channels == cout
             and c.kernel_size == (1,) and c.stride == (1,) and c.dilation == (1,) and c.groups == 1
-            and _ng._pad_of(c) == (0,))
+            and pad_of(c) == (0,))
 
 
 def _depthwise(m, C):
     """the depthwise Conv1d of either form: ``Conv1d(C, C, 31, padding=15, groups=C)``, or a wrapper that pads by (15, 15) and
     then runs an unpadded grouped ``conv``"""
     if isinstance(m, torch.nn.Conv1d):
-        conv, pad = m, _ng._pad_of(m)
+        conv, pad = m, pad_of(m)
         pad = (pad[0], pad[0])
         if m.padding_mode != "zeros":
             return None
     else:
         conv, pad = getattr(m, "conv", None), getattr(m, "padding", None)
-        if not isinstance(conv, torch.nn.Conv1d) or not isinstance(pad, (tuple, list)) or _ng._pad_of(conv) != (0,):
+        if not isinstance(conv, torch.nn.Conv1d) or not isinstance(pad, (tuple, list)) or pad_of(conv) != (0,):
             return None
         if not isinstance(m, torch.nn.Module) or m._forward_pre_hooks or m._forward_hooks:
             return None
@@ -204,7 +189,7 @@ def _conv_spec(module):
 
 def conv_eligible(module, x):
     """the ``(weights, norm, eps)`` to run ``module`` on ``x`` with the HIP kernel, or None: the module's own ``net``"""
-    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() != 3 or x.shape[1] < 1 or not _ng._on_device(x):
+    if not on_device(x, 3) or x.shape[1] < 1:
         return None
     spec = _conv_spec(module)
     if spec is None:
@@ -216,9 +201,9 @@ def conv_eligible(module, x):
     if drop.p != 0 and drop.training:
         return None
     flat = list(weights) + (list(norm) if norm is not None else [])
-    if any(t.device != x.device for t in flat) or _ng._needs_grad([x] + flat):
+    if any(t.device != x.device for t in flat) or needs_grad([x] + flat):
         return None
-    if D in CONV_TORCH_FASTER and (CONV_TORCH_FASTER[D] is None or x.shape[0] * x.shape[1] < CONV_TORCH_FASTER[D]):
+    if torch_faster(CONV_TORCH_FASTER, D, x.shape[0] * x.shape[1]):
         return None
     return weights, norm, eps
 
@@ -276,10 +261,8 @@ def patch_reference_conformer():
             continue
         for cls_name, fwd in (("ConformerConvModule", _conv_module_forward), ("CFNEncoderLayer", _encoder_layer_forward)):
             cls = getattr(mod, cls_name, None)
-            if cls is None or "_reference_forward" in cls.__dict__:
-                continue
-            cls._reference_forward = cls.forward
-            cls.forward = fwd
+            if cls is not None and cls.forward is park(cls, "forward"):
+                cls.forward = fwd
         done.append(mod)
     return done
 
@@ -292,8 +275,5 @@ def unpatch_reference_conformer():
         if mod is None:
             continue
         for cls_name in ("ConformerConvModule", "CFNEncoderLayer"):
-            cls = getattr(mod, cls_name, None)
-            ref = None if cls is None else cls.__dict__.get("_reference_forward")
-            if ref is not None:
-                cls.forward = ref
-                del cls._reference_forward
+            if hasattr(mod, cls_name):
+                unpark(getattr(mod, cls_name), "forward")

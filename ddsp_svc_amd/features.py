@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import _ffi, core
+from ._patching import park, rebind_everywhere, undo_rebound, unpark
 
 TRACK_MODES = {"linear": 0, "nearest": 1}
 N_CLASS = 360
@@ -281,35 +282,25 @@ def patch_reference_features():
     (``Volume_Extractor``, the track's post-processing) are left alone: call ``volume`` / ``f0_track`` from code that keeps its
     block on the device.  Idempotent; returns the ``(module name, attribute)`` pairs it rebound."""
     import importlib
-    from .vocoder import _rebind_everywhere
     swapped = {}
     rcore = importlib.import_module("ddsp.core")
     importlib.import_module("ddsp.vocoder")              # so that its by-name imports exist to be rebound
-    for name, mine in (("MaskedAvgPool1d", core.MaskedAvgPool1d), ("MedianPool1d", core.MedianPool1d)):
-        if hasattr(rcore, name) and not hasattr(rcore, "_reference_" + name):
-            orig = getattr(rcore, name)
-            setattr(rcore, "_reference_" + name, orig)
-            _PARKED.append((rcore, name))
-            swapped[orig] = _dispatch_pool(orig, mine)
     rutils = importlib.import_module("encoder.rmvpe.utils")
     importlib.import_module("encoder.rmvpe.inference")
-    if hasattr(rutils, "to_local_average_f0") and not hasattr(rutils, "_reference_to_local_average_f0"):
-        orig = rutils.to_local_average_f0
-        rutils._reference_to_local_average_f0 = orig
-        _PARKED.append((rutils, "to_local_average_f0"))
-        swapped[orig] = _dispatch_decode(orig)
-    changed = _rebind_everywhere(swapped) if swapped else []
+    for mod, name, mine in ((rcore, "MaskedAvgPool1d", core.MaskedAvgPool1d), (rcore, "MedianPool1d", core.MedianPool1d),
+                            (rutils, "to_local_average_f0", None)):
+        orig = park(mod, name) if hasattr(mod, name) else None
+        if orig is not None and getattr(mod, name) is orig:  # not swapped yet
+            _PARKED.append((mod, name))
+            swapped[orig] = _dispatch_decode(orig) if mine is None else _dispatch_pool(orig, mine)
+    changed = rebind_everywhere(swapped) if swapped else []
     _REBOUND.extend(changed)
     return [(mod.__name__, name) for mod, name, _old, _new in changed]
 
 
 def unpatch_reference_features():
-    """Undo ``patch_reference_features()``: exactly the bindings it changed, where they are still its own."""
-    while _REBOUND:
-        mod, name, old, new = _REBOUND.pop()
-        if getattr(mod, name, None) is new:
-            setattr(mod, name, old)
+    """Undo ``patch_reference_features()``: the originals are bound back where they were parked, and of the other bindings it
+    changed exactly those that are still its own."""
     while _PARKED:
-        mod, name = _PARKED.pop()
-        if hasattr(mod, "_reference_" + name):
-            delattr(mod, "_reference_" + name)
+        unpark(*_PARKED.pop())
+    undo_rebound(_REBOUND)

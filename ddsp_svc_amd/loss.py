@@ -13,6 +13,7 @@ import torch
 
 from . import _ffi
 from ._ffi import ptr
+from ._patching import park
 
 
 def _dense_batch_major(z):
@@ -321,8 +322,7 @@ def patch_reference_loss():
     imported at :7) to the classes above."""
     import sys
     import ddsp.loss as dl
-    if not hasattr(dl, "_reference_RSSLoss"):
-        dl._reference_SSSLoss, dl._reference_RSSLoss = dl.SSSLoss, dl.RSSLoss
+    park(dl, "SSSLoss"), park(dl, "RSSLoss")
     dl.SSSLoss, dl.RSSLoss = SSSLoss, RSSLoss
     tr = sys.modules.get("train")
     if tr is not None and hasattr(tr, "RSSLoss"):

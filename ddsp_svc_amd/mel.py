@@ -19,6 +19,8 @@ from torch.autograd.function import once_differentiable
 
 from . import _ffi
 from ._ffi import ptr
+from ._modules import needs_grad
+from ._patching import park
 
 
 def slaney_mel_filterbank(sr, n_fft, n_mels, fmin, fmax):
@@ -79,7 +81,7 @@ def _bin_filters(basis):
 
 
 def _needs_grad(y):
-    return torch.is_grad_enabled() and getattr(y, "requires_grad", False)
+    return isinstance(y, torch.Tensor) and needs_grad((y,))
 
 
 class _MelSpectrogram(torch.autograd.Function):
@@ -271,10 +273,9 @@ def patch_reference_stft():
     cascades' DDSP loss) takes the HIP autograd node in the plain configuration on the GPU and the reference's
     differentiable torch code everywhere else."""
     import nsf_hifigan.nvSTFT as nv
-    if hasattr(nv.STFT, "_reference_get_mel"):
+    ref_get_mel = park(nv.STFT, "get_mel")
+    if nv.STFT.get_mel is not ref_get_mel:
         return nv
-    ref_get_mel = nv.STFT.get_mel
-    nv.STFT._reference_get_mel = ref_get_mel
 
     def get_mel(self, y, keyshift=0, speed=1, center=False):
         plain = (keyshift == 0 and speed == 1 and not center and self.n_fft == 2048 and self.win_size == 2048 and

@@ -10,6 +10,7 @@ f32 MFMA GEMMs with the intermediate in LDS, and the ``xs / num_kernels`` sum fo
   generator_forward          ``Generator.forward`` of any module with the reference generator's attributes, stage by stage
   patch_reference_generator  rebinds ``ResBlock1.forward`` and ``Generator.forward`` of an importable reference checkout
   unpatch_reference_generator
+  release_workspace, clear_packed   drop the cached hand-over buffers / the cached weight tables (``_modules``)
 
 Dispatch (``hip_eligible``): a float32 tensor on the GPU, no gradient needed, C in {16, 32, 64}, k in {3, 7, 11}, dilations the
 kernel's LDS image holds, and plain ``Conv1d`` weights -- every conv of the block has had ``remove_weight_norm`` applied (the
@@ -32,6 +33,8 @@ import torch
 import torch.nn.functional as F
 
 from . import _ffi
+from ._modules import clear_packed, needs_grad, on_device, packed_table, pad_of, plain, torch_faster  # noqa: F401
+from ._patching import park, unpark
 
 CHANNELS = (16, 32, 64)
 KERNEL_SIZES = (3, 7, 11)
@@ -47,8 +50,6 @@ SEAM_TORCH_FASTER = {}
 HEAD_TORCH_FASTER = {}
 
 _LOCK = threading.Lock()
-_PACKED = {}                                           # key of the weights -> (versions, device table, the tensors kept alive)
-_PACKED_MAX = 256
 # (device, raw handle of the caller's stream) -> the hand-over buffer between pairs, grown on demand and kept; LRU, as _ffi._AUX
 _WS = collections.OrderedDict()
 _WS_MAX = 16
@@ -65,31 +66,18 @@ def _flat(weights):
     return [t for pair in weights for t in pair]
 
 
-def _packed(weights, C, k, device):
-    """the kernel's weight table on ``device``: packed on the host once per set of weight tensors, found again by their
-    ``data_ptr`` and rebuilt when one of them was written in place (``_version``)"""
-    flat = _flat(weights)
-    key = (str(device), C, k) + tuple(t.data_ptr() for t in flat)
-    versions = tuple(t._version for t in flat)
-    hit = _PACKED.get(key)
-    if hit is not None and hit[0] == versions:
-        return hit[1]
-    lib = _ffi.lib()
-    pairs = len(weights)
-    with torch.no_grad():
-        w = torch.stack([t.detach().to("cpu", torch.float32) for pair in weights for t in (pair[0], pair[2])]).contiguous()
-        b = torch.stack([t.detach().to("cpu", torch.float32) for pair in weights for t in (pair[1], pair[3])]).contiguous()
+def _pack(dims, flat):
+    """the host table of one block's ``(w1, b1, w2, b2)`` per pair, for ``packed_table``"""
+    (C, k), pairs, lib = dims, len(flat) // 4, _ffi.lib()
     nbytes = int(lib.ddsp_hip_resblock1_pack_bytes(C, k, pairs))
     if nbytes == 0:
         raise ValueError("resblock1: C = %d, k = %d, %d pairs is outside the kernel's range" % (C, k, pairs))
+    with torch.no_grad():
+        w = torch.stack([t.detach().to("cpu", torch.float32) for t in flat[0::2]]).contiguous()
+        b = torch.stack([t.detach().to("cpu", torch.float32) for t in flat[1::2]]).contiguous()
     host = torch.empty(nbytes // 4, dtype=torch.float32)
     _ffi.check(lib.ddsp_hip_resblock1_pack(w.data_ptr(), b.data_ptr(), C, k, pairs, host.data_ptr(), nbytes))
-    table = host.to(device)
-    with _LOCK:
-        while len(_PACKED) >= _PACKED_MAX:
-            _PACKED.pop(next(iter(_PACKED)))
-        _PACKED[key] = (versions, table, flat)         # the tensors stay alive, so a data_ptr cannot come back as another's
-    return table
+    return host
 
 
 def _workspace(nbytes, x):
@@ -152,7 +140,7 @@ def resblock1(x, weights, dilations, acc=None, scale=None, out=None):
     if B == 0:
         return y
     lib = _ffi.lib()
-    table = _packed(weights, C, k, x.device)
+    table = packed_table("resblock", (C, k), _flat(weights), x.device, _pack)
     pairs = len(dilations)
     nws = int(lib.ddsp_hip_resblock1_workspace_bytes(B, C, T, pairs))
     ws = _workspace(nws, x) if nws else None          # its real size goes to the library, which refuses one too small
@@ -183,28 +171,17 @@ def head_tile(C):
     return int(_ffi.lib().ddsp_hip_output_head_tile(C))
 
 
-def _packed_seam(tensors, Cout, u, s, device):
-    """the seam's weight table on ``device``, cached like ``_packed``'s: by ``data_ptr``, rebuilt on a new ``_version``"""
-    key = (str(device), "seam", Cout, u, s) + tuple(t.data_ptr() for t in tensors)
-    versions = tuple(t._version for t in tensors)
-    hit = _PACKED.get(key)
-    if hit is not None and hit[0] == versions:
-        return hit[1]
+def _pack_seam(dims, tensors):
+    """the host table of a seam's ``(up weight, up bias, noise weight, noise bias)``, for ``packed_table``"""
     lib = _ffi.lib()
-    with torch.no_grad():
-        wu, bu, wn, bn = [t.detach().to("cpu", torch.float32).contiguous() for t in tensors]
-    nbytes = int(lib.ddsp_hip_upsample_stage_pack_bytes(Cout, u, s))
+    nbytes = int(lib.ddsp_hip_upsample_stage_pack_bytes(*dims))
     if nbytes == 0:
-        raise ValueError("upsample_stage: Cout = %d, u = %d, s = %d is outside the kernel's range" % (Cout, u, s))
+        raise ValueError("upsample_stage: Cout = %d, u = %d, s = %d is outside the kernel's range" % dims)
+    with torch.no_grad():
+        staged = [t.detach().to("cpu", torch.float32).contiguous() for t in tensors]
     host = torch.empty(nbytes // 4, dtype=torch.float32)
-    _ffi.check(lib.ddsp_hip_upsample_stage_pack(wu.data_ptr(), bu.data_ptr(), wn.data_ptr(), bn.data_ptr(), Cout, u, s,
-                                                host.data_ptr(), nbytes))
-    table = host.to(device)
-    with _LOCK:
-        while len(_PACKED) >= _PACKED_MAX:
-            _PACKED.pop(next(iter(_PACKED)))
-        _PACKED[key] = (versions, table, list(tensors))
-    return table
+    _ffi.check(lib.ddsp_hip_upsample_stage_pack(*[t.data_ptr() for t in staged], *dims, host.data_ptr(), nbytes))
+    return host
 
 
 def seam_shape_ok(Cin, Cout, u, s):
@@ -240,7 +217,7 @@ def upsample_stage(x, up_weight, up_bias, stride, source, noise_weight, noise_bi
         raise ValueError("upsample_stage: out must be a contiguous float32 [B, Cout, u Tin] tensor")
     if B == 0:
         return y
-    table = _packed_seam((up_weight, up_bias, noise_weight, noise_bias), Cout, u, s, x.device)
+    table = packed_table("seam", (Cout, u, s), (up_weight, up_bias, noise_weight, noise_bias), x.device, _pack_seam)
     CALLS["seam_hip"] += 1
     _ffi.check(_ffi.lib().ddsp_hip_upsample_stage(x.data_ptr(), source.data_ptr(), y.data_ptr(), table.data_ptr(),
                                                   table.numel() * 4, B, Cout, Tin, u, s, _ffi.stream_of(x)))
@@ -277,18 +254,11 @@ def output_head(x, weight, bias, slope=HEAD_SLOPE, out=None):
 # ---- the reference's modules --------------------------------------------------------------------------------------------------
 
 def _plain_conv(c, C, k, d):
-    """a Conv1d the kernel can stand in for: C -> C channels, k taps, dilation d, 'same' zero padding, and a ``weight`` that is
-    a plain parameter (no weight-norm hook or parametrization left on it)"""
-    if not isinstance(c, torch.nn.Conv1d) or not isinstance(c._parameters.get("weight"), torch.Tensor):
-        return False
-    if any(type(h).__name__ == "WeightNorm" for h in c._forward_pre_hooks.values()):
-        return False
-    if c._forward_pre_hooks or c._forward_hooks:       # any other hook expects Conv1d.forward to run
-        return False
-    pad = c.padding if isinstance(c.padding, tuple) else (c.padding,)
-    return (c.in_channels == C and c.out_channels == C and c.kernel_size == (k,) and c.stride == (1,) and c.dilation == (d,)
-            and c.groups == 1 and c.padding_mode == "zeros" and pad == ((k * d - d) // 2,) and c.bias is not None
-            and c.weight.dtype == torch.float32)
+    """a Conv1d the kernel can stand in for: C -> C channels, k taps, dilation d, 'same' zero padding, a bias, and a ``weight``
+    that is a plain parameter (no weight-norm hook or parametrization left on it)"""
+    return (isinstance(c, torch.nn.Conv1d) and plain(c) and c.in_channels == C and c.out_channels == C and c.kernel_size == (k,)
+            and c.stride == (1,) and c.dilation == (d,) and c.groups == 1 and c.padding_mode == "zeros"
+            and pad_of(c) == ((k * d - d) // 2,) and c.bias is not None)
 
 
 def _block_spec(block):
@@ -308,25 +278,14 @@ def _block_spec(block):
     return [(a.weight, a.bias, b.weight, b.bias) for a, b in zip(c1s, c2s)], dil
 
 
-def _on_device(x):
-    try:
-        _ffi.check_device(x)
-    except RuntimeError:
-        return False
-    return True
-
-
 def hip_eligible(block, x):
     """the ``(weights, dilations)`` to run ``block`` on ``x`` with the HIP kernel, or None: the reference's forward"""
-    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() != 3 or x.shape[-1] < 1 or not _on_device(x):
+    if not on_device(x, 3) or x.shape[-1] < 1:
         return None
     spec = _block_spec(block)
     if spec is None or x.shape[1] != spec[0][0][0].shape[0]:
         return None
-    if torch.is_grad_enabled() and (x.requires_grad or any(t.requires_grad for t in _flat(spec[0]))):
-        return None
-    C, k = x.shape[1], spec[0][0][0].shape[-1]
-    if (C, k) in TORCH_FASTER and (TORCH_FASTER[(C, k)] is None or x.shape[-1] < TORCH_FASTER[(C, k)]):
+    if needs_grad([x] + _flat(spec[0])) or torch_faster(TORCH_FASTER, (x.shape[1], spec[0][0][0].shape[-1]), x.shape[-1]):
         return None
     return spec
 
@@ -363,18 +322,9 @@ def stage_forward(blocks, x):
 
 
 def _plain_module(c, cls):
-    """a module of class ``cls`` whose ``weight`` is a plain float32 parameter, with a bias, zero padding, one group, no dilation
-    and no hook (a weight-norm hook recomputes ``weight``; any other expects the module's own forward to run)"""
-    if not isinstance(c, cls) or not isinstance(c._parameters.get("weight"), torch.Tensor):
-        return False
-    if c._forward_pre_hooks or c._forward_hooks:
-        return False
-    return (c.groups == 1 and c.dilation == (1,) and c.padding_mode == "zeros" and c.bias is not None
-            and c.weight.dtype == torch.float32 and c.bias.dtype == torch.float32)
-
-
-def _pad_of(c):
-    return tuple(c.padding) if isinstance(c.padding, (tuple, list)) else (c.padding,)
+    """a module of class ``cls`` whose ``weight`` and bias are plain float32, with zero padding, one group, no dilation and no hook"""
+    return (isinstance(c, cls) and plain(c) and c.groups == 1 and c.dilation == (1,) and c.padding_mode == "zeros"
+            and c.bias is not None and c.bias.dtype == torch.float32)
 
 
 def _seam_spec(up, noise_conv):
@@ -382,29 +332,25 @@ def _seam_spec(up, noise_conv):
     if not _plain_module(up, torch.nn.ConvTranspose1d) or not _plain_module(noise_conv, torch.nn.Conv1d):
         return None
     Cout, u = up.out_channels, up.stride[0]
-    if (up.in_channels != 2 * Cout or up.kernel_size != (2 * u,) or _pad_of(up) != (u // 2,)
+    if (up.in_channels != 2 * Cout or up.kernel_size != (2 * u,) or pad_of(up) != (u // 2,)
             or tuple(up.output_padding) != (0,)):
         return None
     s = noise_conv.stride[0]
     if noise_conv.in_channels != 1 or noise_conv.out_channels != Cout:
         return None
     if noise_conv.kernel_size == (1,):
-        if s != 1 or _pad_of(noise_conv) != (0,):
+        if s != 1 or pad_of(noise_conv) != (0,):
             return None
-    elif s < 2 or noise_conv.kernel_size != (2 * s,) or _pad_of(noise_conv) != (s // 2,):
+    elif s < 2 or noise_conv.kernel_size != (2 * s,) or pad_of(noise_conv) != (s // 2,):
         return None
     if not seam_shape_ok(2 * Cout, Cout, u, s):
         return None
     return Cout, u, s
 
 
-def _needs_grad(tensors):
-    return torch.is_grad_enabled() and any(t.requires_grad for t in tensors)
-
-
 def seam_eligible(up, noise_conv, x, source):
     """``(Cout, u, s)`` to run ``up(lrelu(x)) + noise_conv(source)`` with the HIP kernel, or None: the torch line"""
-    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() != 3 or x.shape[-1] < 1 or not _on_device(x):
+    if not on_device(x, 3) or x.shape[-1] < 1:
         return None
     if not isinstance(source, torch.Tensor) or source.dtype != torch.float32 or source.dim() != 3 or source.device != x.device:
         return None
@@ -414,9 +360,9 @@ def seam_eligible(up, noise_conv, x, source):
     Cout, u, s = spec
     if tuple(source.shape) != (x.shape[0], 1, s * u * x.shape[-1]):
         return None
-    if _needs_grad([x, source, up.weight, up.bias, noise_conv.weight, noise_conv.bias]):
+    if needs_grad([x, source, up.weight, up.bias, noise_conv.weight, noise_conv.bias]):
         return None
-    if (Cout, u) in SEAM_TORCH_FASTER and (SEAM_TORCH_FASTER[(Cout, u)] is None or x.shape[-1] < SEAM_TORCH_FASTER[(Cout, u)]):
+    if torch_faster(SEAM_TORCH_FASTER, (Cout, u), x.shape[-1]):
         return None
     return spec
 
@@ -432,17 +378,17 @@ def seam_forward(up, noise_conv, x, source):
 
 def head_eligible(conv_post, x):
     """True to run ``tanh(conv_post(lrelu(x)))`` with the HIP kernel"""
-    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() != 3 or x.shape[-1] < 1 or not _on_device(x):
+    if not on_device(x, 3) or x.shape[-1] < 1:
         return False
     if not _plain_module(conv_post, torch.nn.Conv1d):
         return False
     C = conv_post.in_channels
     if (C not in CHANNELS or x.shape[1] != C or conv_post.out_channels != 1 or conv_post.kernel_size != (HEAD_TAPS,)
-            or conv_post.stride != (1,) or _pad_of(conv_post) != (3,) or conv_post.weight.device != x.device):
+            or conv_post.stride != (1,) or pad_of(conv_post) != (3,) or conv_post.weight.device != x.device):
         return False
-    if _needs_grad([x, conv_post.weight, conv_post.bias]):
+    if needs_grad([x, conv_post.weight, conv_post.bias]):
         return False
-    return not (C in HEAD_TORCH_FASTER and (HEAD_TORCH_FASTER[C] is None or x.shape[-1] < HEAD_TORCH_FASTER[C]))
+    return not torch_faster(HEAD_TORCH_FASTER, C, x.shape[-1])
 
 
 def head_forward(conv_post, x):
@@ -468,7 +414,7 @@ def generator_forward(gen, x, f0, fallback=None):
         return fallback(gen, x, f0)
     first = gen.resblocks[0] if len(gen.resblocks) else None
     if (getattr(first, "convs1", None) is None or getattr(first, "convs2", None) is None or not isinstance(x, torch.Tensor)
-            or x.dtype != torch.float32 or not _on_device(x)
+            or x.dtype != torch.float32 or not on_device(x)
             or (torch.is_grad_enabled() and any(p.requires_grad for p in gen.parameters()))):
         return fallback(gen, x, f0)
     source = gen.m_source(f0, gen.upp).transpose(1, 2)
@@ -484,17 +430,15 @@ def patch_reference_generator():
     """Route ``nsf_hifigan.models.ResBlock1.forward`` and, in ``Generator.forward`` of an importable reference checkout, each
     stage's upsampling seam, its block sum and the output head through the dispatchers above.  Idempotent; returns the module."""
     import nsf_hifigan.models as nm
-    if hasattr(nm.ResBlock1, "_reference_forward"):
-        return nm
-    nm.ResBlock1._reference_forward = nm.ResBlock1.forward
-    nm.Generator._reference_forward = nm.Generator.forward
-    ref_generator_forward = nm.Generator.forward
+    ref_generator_forward = park(nm.Generator, "forward")
 
     def patched_forward(self, x, f0):
         return generator_forward(self, x, f0, fallback=ref_generator_forward)
 
-    nm.ResBlock1.forward = resblock_forward
-    nm.Generator.forward = patched_forward
+    if nm.Generator.forward is ref_generator_forward:
+        nm.Generator.forward = patched_forward
+    if nm.ResBlock1.forward is park(nm.ResBlock1, "forward"):
+        nm.ResBlock1.forward = resblock_forward
     return nm
 
 
@@ -502,10 +446,6 @@ def unpatch_reference_generator():
     """Undo ``patch_reference_generator()``."""
     import sys
     nm = sys.modules.get("nsf_hifigan.models")
-    if nm is None:
-        return
-    for cls in (nm.ResBlock1, nm.Generator):
-        ref = cls.__dict__.get("_reference_forward")
-        if ref is not None:
-            cls.forward = ref
-            del cls._reference_forward
+    if nm is not None:
+        unpark(nm.ResBlock1, "forward")
+        unpark(nm.Generator, "forward")

@@ -12,6 +12,7 @@ import torch
 
 from . import _ffi
 from ._ffi import ptr
+from ._patching import park
 
 
 def normal_noise(B, T, dim, seed, offset, device):
@@ -116,10 +117,9 @@ def patch_reference_source(in_kernel_noise_seed=None):
     inside the kernel and its ``[B, L*upp, dim]`` tensor -- 1.0 GB at cfg 5's B = 64 x 10 s -- is never allocated."""
     import nsf_hifigan.models as nm
     nm.SourceModuleHnNSF.in_kernel_noise_seed = in_kernel_noise_seed
-    if hasattr(nm.SourceModuleHnNSF, "_reference_forward"):
+    ref_forward = park(nm.SourceModuleHnNSF, "forward")
+    if nm.SourceModuleHnNSF.forward is not ref_forward:
         return nm
-    ref_forward = nm.SourceModuleHnNSF.forward
-    nm.SourceModuleHnNSF._reference_forward = ref_forward
 
     def forward(self, x, upp):
         gen = self.l_sin_gen

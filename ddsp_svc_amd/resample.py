@@ -226,7 +226,7 @@ def patch_reference_resample():
     orig = getattr(ta, "Resample", None) if ta is not None else None
     if orig is None or orig is Resample:
         return []
-    from .vocoder import _rebind_everywhere
+    from ._patching import rebind_everywhere
     skip = [m for name, m in list(sys.modules.items()) if name == "torchaudio" or name.startswith("torchaudio.")]
-    changed = _rebind_everywhere({orig: Resample}, skip=skip)
+    changed = rebind_everywhere({orig: Resample}, skip=skip)
     return [(mod.__name__, name) for mod, name, _old, _new in changed]

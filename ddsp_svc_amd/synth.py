@@ -215,12 +215,6 @@ class SinusoidBankFunction(torch.autograd.Function):
 
 
 # ---- differentiable tap synthesis from raw controls (training path of Sins / CombSub) ------------------------
-def _rows2(t, n):
-    """[B,F,n] control -> (tensor usable as [B*F, n] rows, row stride)"""
-    t, ld = _rows(t, n)
-    return t, ld
-
-
 class MagnitudeTapsFunction(torch.autograd.Function):
     """taps = window(roll(irfft(scale * exp(c)))) (vocoder.py:835-836 + core.py:254-270) with the gradient back to
     the raw control ``c [B,F,n]``; ``mode`` HANN or DYNAMIC (``half_width [B,F]``)."""

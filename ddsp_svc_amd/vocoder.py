@@ -11,6 +11,7 @@ with ``strict=True`` and ``load_model`` / the diffusion cascade / the enhancer k
 import torch
 
 from . import synth
+from ._patching import park, rebind_everywhere, undo_rebound, unpark
 
 
 def _reference_unit2control():
@@ -192,33 +193,6 @@ def _tensors(args, kwargs):
             yield v
 
 
-def _rebind_everywhere(mapping, skip=()):
-    """Every module that bound one of ``mapping``'s keys by name (``from ddsp.core import upsample`` in flask_api.py:12,
-    gui_diff.py:10, main_reflow.py:13, ...; ``from ddsp.vocoder import CombSubFast`` in diffusion/vocoder.py:13) gets the value
-    instead -- found by IDENTITY over ``sys.modules``, so no list of importers has to be kept up to date.  Attributes whose name
-    starts with ``_reference_`` (where the originals are parked) and the modules in ``skip`` are left alone.  Returns the
-    bindings it changed as ``(module, name, old value, new value)`` -- ``unpatch_reference`` undoes exactly those."""
-    import sys
-    ids = {id(k): v for k, v in mapping.items()}
-    changed = []
-    for mod in list(sys.modules.values()):
-        if mod is None or mod in skip:
-            continue
-        try:
-            items = list(vars(mod).items())
-        except TypeError:                                # a module-like object without a __dict__
-            continue
-        for name, val in items:
-            new = ids.get(id(val))
-            if new is not None and not name.startswith("_reference_"):
-                try:
-                    setattr(mod, name, new)
-                    changed.append((mod, name, val, new))
-                except Exception:                        # noqa: BLE001  (read-only module objects)
-                    pass
-    return changed
-
-
 _REBOUND = []                                            # what patch_reference() rebound outside ddsp.core / ddsp.vocoder
 
 
@@ -240,26 +214,24 @@ def patch_reference():
     mine = {"Sins": Sins, "CombSub": CombSub, "CombSubFast": CombSubFast, "CombSubSuperFast": CombSubSuperFast}
     swapped = {}
     for name, cls in mine.items():
-        if not hasattr(rvoc, "_reference_" + name):
-            setattr(rvoc, "_reference_" + name, getattr(rvoc, name))
-        cls._reference_cls = getattr(rvoc, "_reference_" + name)
+        cls._reference_cls = park(rvoc, name)
         setattr(rvoc, name, cls)
         swapped[cls._reference_cls] = cls
     for name in PATCHED_CORE_FUNCTIONS:
         if not hasattr(rcore, name):
             continue
-        if not hasattr(rcore, "_reference_" + name):
-            setattr(rcore, "_reference_" + name, getattr(rcore, name))
+        ref = park(rcore, name)
+        if getattr(rcore, name) is ref:
 
-            def dispatch(*a, __h=getattr(hcore, name), __r=getattr(rcore, name), **k):
+            def dispatch(*a, __h=getattr(hcore, name), __r=ref, **k):
                 ts = list(_tensors(a, k))
                 on_gpu = bool(ts) and all(t.is_cuda for t in ts)
                 plain = all(t.dtype in (torch.float32, torch.complex64) for t in ts)
                 return __h(*a, **k) if on_gpu and plain else __r(*a, **k)
             dispatch.__name__ = name
             setattr(rcore, name, dispatch)
-        swapped[getattr(rcore, "_reference_" + name)] = getattr(rcore, name)
-    _REBOUND.extend(_rebind_everywhere(swapped))
+        swapped[ref] = getattr(rcore, name)
+    _REBOUND.extend(rebind_everywhere(swapped))
     return rvoc
 
 
@@ -268,19 +240,8 @@ def unpatch_reference():
     import ddsp.core as rcore
     import ddsp.vocoder as rvoc
     for name, cls in (("Sins", Sins), ("CombSub", CombSub), ("CombSubFast", CombSubFast), ("CombSubSuperFast", CombSubSuperFast)):
-        ref = getattr(rvoc, "_reference_" + name, None)
-        if ref is None:
-            continue
-        setattr(rvoc, name, ref)
-        delattr(rvoc, "_reference_" + name)
+        unpark(rvoc, name)
         cls._reference_cls = None
     for name in PATCHED_CORE_FUNCTIONS:
-        ref = getattr(rcore, "_reference_" + name, None)
-        if ref is None:
-            continue
-        setattr(rcore, name, ref)
-        delattr(rcore, "_reference_" + name)
-    while _REBOUND:                                      # exactly the bindings patch_reference() changed, if they are still its
-        mod, name, old, new = _REBOUND.pop()
-        if getattr(mod, name, None) is new:
-            setattr(mod, name, old)
+        unpark(rcore, name)
+    undo_rebound(_REBOUND)                               # exactly the bindings patch_reference() changed, if they are still its

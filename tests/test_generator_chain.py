@@ -440,7 +440,7 @@ def test_lengths_vary_with_the_caches_kept(dev):
     gen = S.build(name, dev)
     cases = [S.seeded_inputs(name, 2, L, seed=L) for L in lengths]
     NG.release_workspace()
-    NG._PACKED.clear()
+    NG.clear_packed()
     kept = []
     for mel, f0, source in cases[:4]:
         m, f = _inputs(gen, dev, mel, f0, source)
@@ -452,7 +452,7 @@ def test_lengths_vary_with_the_caches_kept(dev):
     assert grown * 4 == 2 * 2 * 16 * 40 * 16 * 4        # two [2, 16, 640] activations: the largest shape seen, never shrunk
     for L, (mel, f0, source), got in zip(lengths, cases, kept):
         NG.release_workspace()
-        NG._PACKED.clear()
+        NG.clear_packed()
         m, f = _inputs(gen, dev, mel, f0, source)
         assert got["out"].shape == (2, 1, 16 * L) and _walk(gen, m, f, got, "L = %d, cleared caches" % L) == ON_TORCH[name]
     cpu = S.build(name)
