@@ -9,6 +9,7 @@
 #include "resblock.h"
 #include "generator_tail.h"
 #include "conformer_conv.h"
+#include "wavenet_layer.h"
 #include <atomic>
 #include <stdio.h>
 #include <mutex>
@@ -1528,6 +1529,33 @@ int ddsp_hip_conformer_conv(const float* x, float* y, const void* packed, size_t
   if ((reinterpret_cast<uintptr_t>(packed) & 3) || (reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(y) & 15))
     return DDSP_HIP_EINVAL;                            // the kernel reads and writes 4 channels at a time
   launch_conformer_conv(x, y, static_cast<const float*>(packed), B, L, D, norm ? 1 : 0, eps, add_input ? 1 : 0, S(stream));
+  return finish();
+}
+
+
+int ddsp_hip_wavenet_layer_tile(int C, int H) { return wnet::shape_ok(C, H) ? wnet::kTile : 0; }
+
+size_t ddsp_hip_wavenet_layer_pack_bytes(int C, int H) { return wavenet_layer_pack_bytes(C, H); }
+
+int ddsp_hip_wavenet_layer_pack(const float* wdil, const float* bdil, const float* wc, const float* bc, const float* wo,
+                                const float* bo, int C, int H, void* packed, size_t packed_bytes) {
+  if (!wdil || !bdil || !wc || !bc || !wo || !bo || !packed) return DDSP_HIP_EINVAL;
+  const size_t need = wavenet_layer_pack_bytes(C, H);
+  if (need == 0) return DDSP_HIP_ESHAPE;
+  if (packed_bytes < need) return DDSP_HIP_EWS;
+  wavenet_layer_pack(wdil, bdil, wc, bc, wo, bo, C, H, static_cast<float*>(packed));
+  return 0;
+}
+
+int ddsp_hip_wavenet_layer(const float* x, const float* cond, const float* d, float* x_out, float* skip, const void* packed,
+                           size_t packed_bytes, int B, long T, int C, int H, int skip_mode, void* stream) {
+  if (B < 0 || T < 1 || (skip_mode != 0 && skip_mode != 1)) return DDSP_HIP_EINVAL;
+  if (!wnet::shape_ok(C, H) || T > (1L << 40)) return DDSP_HIP_ESHAPE;
+  if (B == 0) return 0;
+  if (!x || !cond || !d || !x_out || !skip || !packed || x_out == x || skip == x || skip == x_out) return DDSP_HIP_EINVAL;
+  if (packed_bytes < wavenet_layer_pack_bytes(C, H)) return DDSP_HIP_EWS;
+  if (reinterpret_cast<uintptr_t>(packed) & 3) return DDSP_HIP_EINVAL;
+  launch_wavenet_layer(x, cond, d, x_out, skip, static_cast<const float*>(packed), B, T, C, H, skip_mode, S(stream));
   return finish();
 }
 

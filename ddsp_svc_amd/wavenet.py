@@ -1,0 +1,278 @@
+"""The residual layer of the diffusion denoiser's WaveNet (``ResidualBlock`` of ``diffusion.wavenet``) on HIP:
+csrc/wavenet_layer.h, one launch per layer call, the 3-tap convolution with the conditioner projection and the output projection
+as f32 MFMA GEMMs, the gate between them on the CU, the skip sum accumulated in place.
+
+  tile                        frames per workgroup (``ddsp_hip_wavenet_layer_tile``)
+  residual_layer              the functional form: ``x [B, C, T]``, ``cond [B, H, T]``, ``d [B, C]``, ``(wdil, bdil, wc, bc, wo, bo)``
+  residual_stack              all layers of a WaveNet: one matmul for every layer's step projection, one launch per layer
+  layer_forward / net_forward the dispatchers bound as ``ResidualBlock.forward`` / ``WaveNet.forward``
+  patch_reference_wavenet     rebinds those two in ``diffusion.wavenet``; opt-in (``patch_reference`` leaves it)
+  unpatch_reference_wavenet
+
+Dispatch (``layer_eligible``) is decided from a module's structure, not its class: a ``dilated_conv`` ``Conv1d(C, 2 C, 3,
+padding 1, dilation 1)`` with zeros padding, a ``conditioner_projection`` ``Conv1d(H, 2 C, 1)``, an ``output_projection``
+``Conv1d(C, 2 C, 1)`` and a ``diffusion_projection`` ``Linear(C, C)``, plain float32 parameters without hooks, float32 tensors on
+the GPU, no gradient needed, autocast off, (C, H) = (384, 256) or (512, 256).  Everything else runs the module's own forward.
+``LAYER_TORCH_FASTER`` maps C to the number of frames B T below which the same-GPU torch chain was measured faster
+(tools/wavenet_bench.py); None: at every size, which is also what a C without a committed measurement gets.
+"""
+import math
+import threading
+
+import torch
+
+from . import _ffi
+from ._modules import needs_grad, on_device, packed_table, pad_of, plain, torch_faster
+from ._patching import park, unpark
+
+SHAPES = ((384, 256), (512, 256))
+# C -> the number of frames B T below which the torch op chain was measured faster on the same GPU (None: at every size; the
+# hook then routes nothing for that C, the functional API still runs the kernel).  tools/wavenet_bench.py on one MI355X
+# (profiles/wavenet_throughput.json, wavenet_latency.json): at both C torch is faster at 1 x 100, 1 x 203 and 48 x 172 = 8 256
+# frames, the kernel at 32 x 862 = 27 584, the smallest size at which it was seen to win (x 1.20 at C = 384, x 1.04 at C = 512),
+# and at 64 x 862 (x 1.18, x 1.04).
+LAYER_TORCH_FASTER = {384: 27584, 512: 27584}
+# dispatch counters (tests and tools read them): layer calls; separate from conformer.CALLS
+CALLS = {"hip": 0, "reference": 0}
+PACKS = {"count": 0}                                   # weight tables built (a cache hit does not count)
+_LOCK = threading.Lock()
+_STACKED = {}                                          # data_ptrs of the projection weights -> (versions, W [n C, C], b [n C], kept)
+_STACKED_MAX = 16
+
+
+def tile(C, H):
+    """frames per workgroup (``ddsp_hip_wavenet_layer_tile``); 0 for a (C, H) the kernel does not take"""
+    return int(_ffi.lib().ddsp_hip_wavenet_layer_tile(int(C), int(H)))
+
+
+def _pack(dims, flat):
+    """the host table of ``(wdil, bdil, wc, bc, wo, bo)``, for ``packed_table``"""
+    (C, H), lib = dims, _ffi.lib()
+    nbytes = int(lib.ddsp_hip_wavenet_layer_pack_bytes(C, H))
+    if nbytes == 0:
+        raise ValueError("residual_layer: (C, H) = (%d, %d) is outside the kernel's range" % (C, H))
+    with torch.no_grad():
+        staged = [t.detach().to("cpu", torch.float32).contiguous() for t in flat]
+    host = torch.empty(nbytes // 4, dtype=torch.float32)
+    _ffi.check(lib.ddsp_hip_wavenet_layer_pack(*[t.data_ptr() for t in staged], C, H, host.data_ptr(), nbytes))
+    PACKS["count"] += 1
+    return host
+
+
+def _check_weights(weights, C, H):
+    if len(weights) != 6:
+        raise ValueError("residual_layer: weights must be (wdil, bdil, wc, bc, wo, bo)")
+    want = ((2 * C, C, 3), (2 * C,), (2 * C, H, 1), (2 * C,), (2 * C, C, 1), (2 * C,))
+    if any(tuple(t.shape) != s for t, s in zip(weights, want)):
+        raise ValueError("residual_layer: weights must be [2 C, C, 3], [2 C], [2 C, H, 1], [2 C], [2 C, C, 1], [2 C]")
+
+
+def _result(name, t, like):
+    if t is None:
+        return torch.empty_like(like)
+    if not t.is_contiguous() or t.shape != like.shape or t.dtype != torch.float32:
+        raise ValueError("residual_layer: %s must be a contiguous float32 tensor of x's shape" % name)
+    return t
+
+
+def residual_layer(x, cond, d, weights, out=None, skip=None, accumulate=False):
+    """One residual layer on the HIP kernel: ``x [B, C, T]``, ``cond [B, H, T]``, ``d [B, C]`` (the layer's projection of the
+    step embedding), ``weights = (wdil [2 C, C, 3], bdil [2 C], wc [2 C, H, 1], bc [2 C], wo [2 C, C, 1], bo [2 C])``, all float32.
+    Returns ``(x_out, skip)``: ``(x + residual) / sqrt 2`` in ``out`` and the skip half in ``skip`` -- with ``accumulate`` ADDED
+    to what ``skip`` holds.  ``out`` must not be ``x`` (a tile reads its neighbours' frames).  No synchronisation; once the weight
+    table exists the only allocations are the results that were not given, so a call can be captured in a graph."""
+    _ffi.check_device(x, cond, d, out, skip)
+    if x.dtype != torch.float32 or x.dim() != 3 or cond.dtype != torch.float32 or cond.dim() != 3 or d.dtype != torch.float32:
+        raise ValueError("residual_layer: x [B, C, T], cond [B, H, T] and d [B, C] must be float32 tensors")
+    B, C, T = x.shape
+    H = cond.shape[1]
+    if (C, H) not in SHAPES:
+        raise ValueError("residual_layer: (C, H) = (%d, %d) is outside the kernel's range" % (C, H))
+    if cond.shape[0] != B or cond.shape[2] != T or tuple(d.shape) != (B, C):
+        raise ValueError("residual_layer: cond must be [B, H, T] and d [B, C]")
+    _check_weights(weights, C, H)
+    if T < 1:
+        raise ValueError("residual_layer: T must be positive")
+    if out is x or skip is x or (out is not None and out is skip):
+        raise ValueError("residual_layer: out and skip must be two tensors, neither of them x")
+    if accumulate and skip is None:
+        raise ValueError("residual_layer: accumulate needs the skip buffer to add to")
+    x, cond, d = x.contiguous(), cond.contiguous(), d.contiguous()
+    y, s = _result("out", out, x), _result("skip", skip, x)
+    if B == 0:
+        return y, s
+    table = packed_table("wavenet", (C, H), list(weights), x.device, _pack)
+    CALLS["hip"] += 1
+    _ffi.check(_ffi.lib().ddsp_hip_wavenet_layer(x.data_ptr(), cond.data_ptr(), d.data_ptr(), y.data_ptr(), s.data_ptr(),
+                                                 table.data_ptr(), table.numel() * 4, B, T, C, H, 1 if accumulate else 0,
+                                                 _ffi.stream_of(x)))
+    return y, s
+
+
+def _stacked_projection(projs):
+    """``(W [n C, C], b [n C])``: the layers' ``(weight [C, C], bias [C])`` step projections stacked, cached by the rule of
+    ``_modules.packed_table`` (found again by every tensor's ``data_ptr``, a hit while every ``_version`` is unchanged)"""
+    flat = [t for p in projs for t in p]
+    key = tuple(t.data_ptr() for t in flat)
+    versions = tuple(t._version for t in flat)
+    with _LOCK:
+        hit = _STACKED.get(key)
+        if hit is not None and hit[0] == versions:
+            return hit[1], hit[2]
+        with torch.no_grad():
+            W = torch.cat([p[0].detach() for p in projs], 0).contiguous()
+            b = torch.cat([p[1].detach() for p in projs], 0).contiguous()
+        while len(_STACKED) >= _STACKED_MAX:
+            _STACKED.pop(next(iter(_STACKED)))
+        _STACKED[key] = (versions, W, b, flat)
+    return W, b
+
+
+def residual_stack(x, cond, s, layers):
+    """The residual layers of a WaveNet: ``x [B, C, T]``, ``cond [B, H, T]``, ``s [B, C]`` (the step embedding after the mlp),
+    ``layers`` a list of ``(weights, (wp [C, C], bp [C]))``.  The projections of all layers are ONE matmul; then one launch per
+    layer, x handed over through two buffers (the caller's x is never written), the first layer stores its skip half and the
+    others add theirs to it.  Returns ``(x after the last layer, the sum of the skips)``."""
+    if not layers:
+        raise ValueError("residual_stack: no layers")
+    n, C = len(layers), x.shape[1]
+    W, b = _stacked_projection([p for _, p in layers])
+    d = torch.addmm(b, s, W.t()).view(s.shape[0], n, C).transpose(0, 1).contiguous()     # [n, B, C]
+    cond = cond.contiguous()
+    bufs = (torch.empty_like(x, memory_format=torch.contiguous_format),
+            torch.empty_like(x, memory_format=torch.contiguous_format) if n > 1 else None)
+    skip = torch.empty_like(bufs[0])
+    src = x
+    for i, (weights, _) in enumerate(layers):
+        dst = bufs[i % 2]
+        residual_layer(src, cond, d[i], weights, out=dst, skip=skip, accumulate=i > 0)
+        src = dst
+    return src, skip
+
+
+# ---- the reference's modules --------------------------------------------------------------------------------------------------
+
+def _plain(m):
+    """``_modules.plain`` and a bias that is a plain float32 parameter too"""
+    return plain(m) and isinstance(m._parameters.get("bias"), torch.Tensor) and m.bias.dtype == torch.float32
+
+
+def _conv(c, cin, cout, k, pad):
+    return (isinstance(c, torch.nn.Conv1d) and _plain(c) and c.in_channels == cin and c.out_channels == cout
+            and c.kernel_size == (k,) and c.stride == (1,) and c.dilation == (1,) and c.groups == 1 and pad_of(c) == (pad,)
+            and c.padding_mode == "zeros")
+
+
+def _layer_spec(block):
+    """``(weights, (wp, bp))`` of a module with the residual block's four submodules in the kernel's shapes, or None"""
+    dil, proj = getattr(block, "dilated_conv", None), getattr(block, "diffusion_projection", None)
+    cp, op = getattr(block, "conditioner_projection", None), getattr(block, "output_projection", None)
+    if not isinstance(block, torch.nn.Module) or block._forward_pre_hooks or block._forward_hooks:
+        return None
+    if not isinstance(dil, torch.nn.Conv1d) or not isinstance(cp, torch.nn.Conv1d):
+        return None
+    C, H = dil.in_channels, cp.in_channels
+    if getattr(block, "residual_channels", C) != C:
+        return None
+    if not _conv(dil, C, 2 * C, 3, 1) or not _conv(cp, H, 2 * C, 1, 0) or not _conv(op, C, 2 * C, 1, 0):
+        return None
+    if not isinstance(proj, torch.nn.Linear) or not _plain(proj) or proj.in_features != C or proj.out_features != C:
+        return None
+    return (dil.weight, dil.bias, cp.weight, cp.bias, op.weight, op.bias), (proj.weight, proj.bias)
+
+
+def layer_eligible(block, x, cond, s):
+    """the ``(weights, (wp, bp))`` to run ``block`` on ``(x, cond, s)`` with the HIP kernel, or None: the block's own forward"""
+    if not on_device(x, 3) or not on_device(cond, 3) or not on_device(s, 2) or x.shape[2] < 1:
+        return None
+    if torch.is_autocast_enabled(x.device.type):
+        return None
+    spec = _layer_spec(block)
+    if spec is None:
+        return None
+    weights, proj = spec
+    C, H = weights[0].shape[1], weights[2].shape[1]
+    B, T = x.shape[0], x.shape[2]
+    if (C, H) not in SHAPES or x.shape[1] != C or tuple(cond.shape) != (B, H, T) or tuple(s.shape) != (B, C):
+        return None
+    flat = list(weights) + list(proj)
+    if any(t.device != x.device for t in flat + [cond, s]) or needs_grad([x, cond, s] + flat):
+        return None
+    if torch_faster(LAYER_TORCH_FASTER, C, B * T):
+        return None
+    return spec
+
+
+def _reference_layer_forward(block, x, conditioner, diffusion_step):
+    CALLS["reference"] += 1
+    ref = getattr(type(block), "_reference_forward", None)
+    if ref is not None:
+        return ref(block, x, conditioner, diffusion_step)
+    return block.reference_forward(x, conditioner, diffusion_step)
+
+
+def layer_forward(block, x, conditioner, diffusion_step):
+    """the dispatcher bound as ``ResidualBlock.forward``"""
+    spec = layer_eligible(block, x, conditioner, diffusion_step)
+    if spec is None:
+        return _reference_layer_forward(block, x, conditioner, diffusion_step)
+    weights, (wp, bp) = spec
+    return residual_layer(x, conditioner, torch.addmm(bp, diffusion_step, wp.t()), weights)
+
+
+def net_forward(wavenet, spec, diffusion_step, cond):
+    """the dispatcher bound as ``WaveNet.forward``: the module's own submodules around the residual layers; the layers as
+    ``residual_stack`` when every one of them is eligible, each through its own forward otherwise"""
+    x = torch.relu(wavenet.input_projection(spec.squeeze(1)))
+    s = wavenet.mlp(wavenet.diffusion_embedding(diffusion_step))
+    blocks = list(wavenet.residual_layers)
+    specs = [layer_eligible(blk, x, cond, s) for blk in blocks] if blocks else [None]
+    if all(sp is not None for sp in specs):
+        _, total = residual_stack(x, cond, s, specs)
+    else:
+        skips = []
+        for blk in blocks:
+            x, skip = blk(x, cond, s)
+            skips.append(skip)
+        total = torch.sum(torch.stack(skips), dim=0)
+    x = total / math.sqrt(len(blocks))
+    x = torch.relu(wavenet.skip_projection(x))
+    return wavenet.output_projection(x)[:, None, :, :]
+
+
+_REFERENCE_MODULE = "diffusion.wavenet"
+
+
+def _block_forward(self, x, conditioner, diffusion_step):
+    return layer_forward(self, x, conditioner, diffusion_step)
+
+
+def _wavenet_forward(self, spec, diffusion_step, cond):
+    return net_forward(self, spec, diffusion_step, cond)
+
+
+def patch_reference_wavenet():
+    """Route ``ResidualBlock.forward`` and ``WaveNet.forward`` of ``diffusion.wavenet`` through the dispatchers above.
+    Idempotent; returns the module, or None when it does not import.  ``vocoder.patch_reference()`` does not call it: the hook
+    is opt-in."""
+    import importlib
+    try:
+        mod = importlib.import_module(_REFERENCE_MODULE)
+    except Exception:                                  # not importable here: nothing to patch
+        return None
+    for cls_name, fwd in (("ResidualBlock", _block_forward), ("WaveNet", _wavenet_forward)):
+        cls = getattr(mod, cls_name, None)
+        if cls is not None and cls.forward is park(cls, "forward"):
+            cls.forward = fwd
+    return mod
+
+
+def unpatch_reference_wavenet():
+    """Undo ``patch_reference_wavenet()``."""
+    import sys
+    mod = sys.modules.get(_REFERENCE_MODULE)
+    if mod is None:
+        return
+    for cls_name in ("ResidualBlock", "WaveNet"):
+        if hasattr(mod, cls_name):
+            unpark(getattr(mod, cls_name), "forward")

@@ -14,7 +14,7 @@
  *     T = F*hop; control tensors take a row stride `ld` (floats between consecutive frames) so
  *     the torch.split views of Unit2Control's output can be passed without a copy;
  *   - more than 65 535 utterances in one call (a grid's limit in y and z): ddsp_hip_resblock1, ddsp_hip_upsample_stage,
- *     ddsp_hip_output_head, ddsp_hip_conformer_conv, ddsp_hip_resample and ddsp_hip_mel_shifted_spectrogram split the batch into launches of 65 535; ddsp_hip_fast_source and
+ *     ddsp_hip_output_head, ddsp_hip_conformer_conv, ddsp_hip_wavenet_layer, ddsp_hip_resample and ddsp_hip_mel_shifted_spectrogram split the batch into launches of 65 535; ddsp_hip_fast_source and
  *     ddsp_hip_combsubsuperfast_synth run their exciter on a flat grid then; ddsp_hip_sine_source(_drawn),
  *     ddsp_hip_spectral_loss(_backward), ddsp_hip_stft_loss(_backward), ddsp_hip_mel_spectrogram_backward,
  *     ddsp_hip_sola_splice, ddsp_hip_volume, ddsp_hip_gate, ddsp_hip_pool1d, ddsp_hip_fft_convolve with
@@ -602,6 +602,28 @@ int ddsp_hip_conformer_conv_pack(const float* w1, const float* b1, const float* 
                                  const float* gamma, const float* beta, int D, void* packed, size_t packed_bytes);
 int ddsp_hip_conformer_conv(const float* x, float* y, const void* packed, size_t packed_bytes, int B, long L, int D, int norm,
                             float eps, int add_input, void* stream);
+
+/* The residual layer of the diffusion denoiser's WaveNet (diffusion/wavenet.py:31-61, ResidualBlock with dilation 1),
+ * csrc/wavenet_layer.h.  As above, these entry points came after version 165 without a version step.
+ *   z = Conv1d(C, 2 C, 3, padding 1)(x + d) + Conv1d(H, 2 C, 1)(cond);  g = sigmoid(z[:C]) tanh(z[C:]);  o = Conv1d(C, 2 C, 1)(g)
+ *   x_out = (x + o[:C]) / sqrt(2);  skip = o[C:]
+ * over x [B, C, T], cond [B, H, T], d [B, C] (the layer's projection of the step embedding), x_out and skip [B, C, T], all
+ * contiguous float32 with no alignment beyond 4 bytes; the 3-tap convolution is a cross-correlation that zero-pads x + d.
+ * (C, H) = (384, 256) or (512, 256) (DDSP_HIP_ESHAPE otherwise), forward only.
+ * ddsp_hip_wavenet_layer_tile: frames per workgroup (64); 0 for a (C, H) the kernel does not take.
+ * ddsp_hip_wavenet_layer_pack_bytes / _pack: HOST weights wdil [2 C][C][3], bdil [2 C], wc [2 C][H], bc [2 C], wo [2 C][C],
+ * bo [2 C] -> the table the kernel reads, written to HOST memory (the caller copies it to the device once and keeps it).
+ * 0 bytes / DDSP_HIP_ESHAPE out of range, DDSP_HIP_EWS short.
+ * ddsp_hip_wavenet_layer: skip_mode 0 stores the skip rows, 1 adds them to what skip holds (the running sum over the layers
+ * of a stack; a tile owns its frames: no atomics).  1 <= T <= 2^40 (DDSP_HIP_EINVAL / DDSP_HIP_ESHAPE); x_out must not be x
+ * (a tile reads its neighbours' frames) and skip neither of them (DDSP_HIP_EINVAL); B = 0 is a no-op.  One launch (per 65 535
+ * utterances), f32 MFMA, 138 KB of LDS per workgroup at C = 512.  No workspace, no allocation, no synchronisation. */
+int ddsp_hip_wavenet_layer_tile(int C, int H);
+size_t ddsp_hip_wavenet_layer_pack_bytes(int C, int H);
+int ddsp_hip_wavenet_layer_pack(const float* wdil, const float* bdil, const float* wc, const float* bc, const float* wo,
+                                const float* bo, int C, int H, void* packed, size_t packed_bytes);
+int ddsp_hip_wavenet_layer(const float* x, const float* cond, const float* d, float* x_out, float* skip, const void* packed,
+                           size_t packed_bytes, int B, long T, int C, int H, int skip_mode, void* stream);
 
 #ifdef __cplusplus
 }
