@@ -8,6 +8,7 @@ Sins/CombSub forward pass of yxlllc/DDSP-SVC).
   nsf_source -- nsf_hifigan.models.SourceModuleHnNSF (SineGen + merge), the vocoder's harmonic source
   nsf_generator -- nsf_hifigan.models.ResBlock1 and the per-stage block sum of Generator.forward: fused f32 MFMA conv pairs
   conformer -- the control network's ConformerConvModule / conv-only CFNEncoderLayer: one fused f32 MFMA launch per module
+  attention -- PCmer's performer attention (FastAttention / SelfAttention): two fused f32 MFMA launches per call
   wavenet   -- the diffusion denoiser's WaveNet ResidualBlock: one fused f32 MFMA launch per layer, the skip sum in place
   loss      -- ddsp/loss.py SSSLoss / RSSLoss (the STFT of any size below 2049 as an in-kernel chirp-z transform, the loss and
                its gradient in the same kernels; torch.stft only above that)
@@ -16,6 +17,6 @@ Sins/CombSub forward pass of yxlllc/DDSP-SVC).
   features  -- the frame features of the real-time path: volume, silence mask / gate, salience decode, F0 track
   sharding  -- utterance sharding across the GPUs of a node (+ optional RCCL gather)
 """
-from . import _ffi, build, conformer, core, features, loss, mel, nsf_generator, nsf_source, resample, splice, synth, wavenet  # noqa: F401
+from . import _ffi, attention, build, conformer, core, features, loss, mel, nsf_generator, nsf_source, resample, splice, synth, wavenet  # noqa: F401
 
 __version__ = "0.1.0"

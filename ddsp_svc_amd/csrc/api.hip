@@ -10,6 +10,7 @@
 #include "generator_tail.h"
 #include "conformer_conv.h"
 #include "wavenet_layer.h"
+#include "performer_attention.h"
 #include <atomic>
 #include <stdio.h>
 #include <mutex>
@@ -1556,6 +1557,49 @@ int ddsp_hip_wavenet_layer(const float* x, const float* cond, const float* d, fl
   if (packed_bytes < wavenet_layer_pack_bytes(C, H)) return DDSP_HIP_EWS;
   if (reinterpret_cast<uintptr_t>(packed) & 3) return DDSP_HIP_EINVAL;
   launch_wavenet_layer(x, cond, d, x_out, skip, static_cast<const float*>(packed), B, T, C, H, skip_mode, S(stream));
+  return finish();
+}
+
+int ddsp_hip_performer_tile(int d, int m) { return perf::shape_ok(d, m) ? perf::kTile : 0; }
+
+size_t ddsp_hip_performer_pack_bytes(int d, int m) { return performer_pack_bytes(d, m); }
+
+int ddsp_hip_performer_pack(const float* proj, int d, int m, void* table, size_t table_bytes) {
+  if (!proj || !table) return DDSP_HIP_EINVAL;
+  const size_t need = performer_pack_bytes(d, m);
+  if (need == 0) return DDSP_HIP_ESHAPE;
+  if (table_bytes < need) return DDSP_HIP_EWS;
+  performer_pack(proj, static_cast<float*>(table));
+  return 0;
+}
+
+int ddsp_hip_performer_chunks(long B, int H, long N) {
+  if (B < 0 || H < 1 || N < 1) return 0;
+  return performer_chunks(B, H, N);
+}
+
+size_t ddsp_hip_performer_workspace_bytes(long B, int H, long N, int chunks) {
+  if (B < 0 || H < 1 || N < 1 || chunks < 1 || N > (1L << 30)) return 0;
+  if ((double)B * H * (double)perf::tiles_of(N) > 2147483647.0) return 0;
+  return performer_ws_bytes(B, H, N, chunks);
+}
+
+int ddsp_hip_performer_attention(const float* q, const float* k, const float* v, float* out, const long* strides,
+                                 const void* table, size_t table_bytes, void* ws, size_t ws_bytes, long B, int H, long N, int d,
+                                 int m, int normalize, int chunks, void* stream) {
+  if (B < 0 || H < 1 || N < 1 || chunks < 1) return DDSP_HIP_EINVAL;
+  if (!perf::shape_ok(d, m) || N > (1L << 30)) return DDSP_HIP_ESHAPE;
+  if ((double)B * H * (double)perf::tiles_of(N) > 2147483647.0) return DDSP_HIP_ESHAPE;   // the grids are flat in x
+  if (B == 0) return 0;
+  if (!q || !k || !v || !out || !strides || !table || !ws || out == q || out == k || out == v) return DDSP_HIP_EINVAL;
+  for (int i = 0; i < 12; ++i)                         // rows are read and written 4 floats at a time
+    if (strides[i] < 0 || (strides[i] & 3)) return DDSP_HIP_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(q) & 15) || (reinterpret_cast<uintptr_t>(k) & 15) || (reinterpret_cast<uintptr_t>(v) & 15) ||
+      (reinterpret_cast<uintptr_t>(out) & 15) || (reinterpret_cast<uintptr_t>(table) & 3) || (reinterpret_cast<uintptr_t>(ws) & 15))
+    return DDSP_HIP_EINVAL;
+  if (table_bytes < performer_pack_bytes(d, m) || ws_bytes < performer_ws_bytes(B, H, N, chunks)) return DDSP_HIP_EWS;
+  launch_performer_attention(q, k, v, out, strides, static_cast<const float*>(table), static_cast<float*>(ws), B, H, N,
+                             normalize ? 1 : 0, chunks, S(stream));
   return finish();
 }
 

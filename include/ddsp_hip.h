@@ -625,6 +625,35 @@ int ddsp_hip_wavenet_layer_pack(const float* wdil, const float* bdil, const floa
 int ddsp_hip_wavenet_layer(const float* x, const float* cond, const float* d, float* x_out, float* skip, const void* packed,
                            size_t packed_bytes, int B, long T, int C, int H, int skip_mode, void* stream);
 
+/* The performer (softmax-kernel linear) attention of PCmer (ddsp/pcmer.py:14-47, 218-232, 297-325), csrc/performer_attention.h.
+ * As above, these entry points came after version 165 without a version step.  Per batch item and head, q, k, v [N, d], the
+ * projection P [m, d], dn = d^-0.25, ratio = m^-0.5:
+ *   (normalize)  q = q / (|q| + 1e-8), k = k / (|k| + 1e-8)
+ *   q' = ratio (exp(dn q P^T - |q|^2 dn^2 / 2 - rowmax(dn q P^T)) + 1e-4);  k' = ratio exp(dn k P^T - |k|^2 dn^2 / 2 + 1e-4)
+ *   out = (q' (k'^T v)) / (q' . sum_n k' + 1e-8)
+ * (d, m) = (64, 266) (DDSP_HIP_ESHAPE otherwise), float32, forward only, no mask.
+ * ddsp_hip_performer_tile: frames per workgroup (64); 0 for anything but (64, 266).
+ * ddsp_hip_performer_pack_bytes / _pack: the HOST projection [m][d] -> the table the kernels read, written to HOST memory (the
+ * caller copies it to the device once and keeps it).  0 bytes / DDSP_HIP_ESHAPE out of range, DDSP_HIP_EWS short.
+ * ddsp_hip_performer_chunks: the default number of key chunks: B H chunks workgroups fill 256 CUs, at most ceil(N / tile).
+ * ddsp_hip_performer_workspace_bytes: B H min(chunks, ceil(N / tile)) partial blocks of (272 x 64 + 272) floats; 0 for
+ * arguments the call below refuses.
+ * ddsp_hip_performer_attention: strides is a HOST array of 12 longs, the (batch, head, frame) strides in floats of q, k, v
+ * and out, whose d elements are contiguous; strides are non-negative multiples of 4 and the four pointers and ws 16-byte
+ * aligned (DDSP_HIP_EINVAL); out must be none of q, k, v.  The three slices of one [B, N, 3 H d] projection result and a
+ * [B, N, H d] result can be passed as they are.  1 <= N <= 2^30 and B H ceil(N / tile) < 2^31 (DDSP_HIP_ESHAPE); chunks >= 1, a
+ * count above ceil(N / tile) is clamped; B = 0 is a no-op.  Two launches on the stream (keys, then queries), both grids flat
+ * in x: no 65 535 limit.  The key partials are added in chunk order: a call is reproducible.  No allocation, no
+ * synchronisation. */
+int ddsp_hip_performer_tile(int d, int m);
+size_t ddsp_hip_performer_pack_bytes(int d, int m);
+int ddsp_hip_performer_pack(const float* proj, int d, int m, void* table, size_t table_bytes);
+int ddsp_hip_performer_chunks(long B, int H, long N);
+size_t ddsp_hip_performer_workspace_bytes(long B, int H, long N, int chunks);
+int ddsp_hip_performer_attention(const float* q, const float* k, const float* v, float* out, const long* strides,
+                                 const void* table, size_t table_bytes, void* ws, size_t ws_bytes, long B, int H, long N, int d,
+                                 int m, int normalize, int chunks, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
