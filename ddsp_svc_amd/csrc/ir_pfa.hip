@@ -267,6 +267,72 @@ __device__ __forceinline__ unsigned wave_incl_scan_u32(unsigned v) {
   return v;
 }
 
+// ---- stage B's fixed output map of the real kinds in closed form (the front launch that carries it runs at the vector pipe's rate, and
+// most of what that stage issued around its DFT-30 was index arithmetic and branches: EXPERIMENTS 6.19) ----
+// |a - b| + c of non-negative integers, b a compile-time constant: ONE instruction, the sum of absolute differences with its addend
+// (the compiler expands the C++ form into subtract / subtract / compare / select / add)
+__device__ __forceinline__ unsigned sad(unsigned a, unsigned b, unsigned c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  unsigned r;
+  asm("v_sad_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "s"(b), "v"(c));
+  return r;
+#else
+  return (a > b ? a - b : b - a) + c;
+#endif
+}
+__device__ __forceinline__ unsigned sad(unsigned a, unsigned b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  unsigned r;
+  asm("v_sad_u32 %0, %1, %2, 0" : "=v"(r) : "v"(a), "s"(b));
+  return r;
+#else
+  return a > b ? a - b : b - a;
+#endif
+}
+// the residue of x >= 0 mod N in (-N/2, N/2]
+constexpr int signed_residue(int x) { return x % NT > HALF ? x % NT - NT : x % NT; }
+static_assert(signed_residue(391 * 15) == HALF, "m = N/2 is output k2 = 15 of row k1 = 0");
+
+// Stage B's store of an EVEN response (rows k1 = 0 .. 8 of a real kind): output k2 of row k1 is tap m = (120 k1 + 391 k2) mod N, rolled
+// to j = (m + N/2) mod N, and lands at the one of j, N - j at or below N/2 -- and at its mirror image in whole rows.  With the signed
+// residues a of 120 k1 (per thread) and c of 391 k2 (a constant per unrolled k2) that position is jl = | N/2 - |a + c| |: two absolute
+// differences, in BYTES and with the row's offset as the second one's addend, so they yield the address.  Row k1 = 0 holds both j and
+// N - j of its own and stores the one at j <= N/2 only (0 < c < N/2 is the other one: a compile-time set of k2), and jl = 0, which has
+// no mirror image, is (k1, k2) = (0, 15) alone: everything conditional is ONE block under k1 != 0 instead of two tests per output.
+template <bool HALF_ROWS>
+__device__ __forceinline__ void store_even_rows(float* O, int t, int k1, const f32x2 (&v)[30]) {
+  constexpr int RL = HALF_ROWS ? NB : NT;                   // floats per staged row
+  char* const Ob = reinterpret_cast<char*>(O);
+  const unsigned row_b = 4u * (unsigned)(2 * t * RL);       // rows 2t (x) and 2t + 1 (y) of the staging
+  const unsigned mirror_b = 2u * row_b + 4u * NT;           // jl -> N - jl in the same row, as byte offsets
+  unsigned y = 120u * (unsigned)k1 + (HALF - 1);            // a + N/2 - 1 = (120 k1 + N/2 - 1) mod N: k1 <= 8, at most two wraps,
+  y = min(y, y - NT);                                       // each the unsigned minimum with the wrapped value
+  y = min(y, y - NT);
+  const unsigned ap = 4u * (y + 1u);                        // 4 (a + N/2), a + N/2 in [1, N]
+  auto put = [&](unsigned at, f32x2 val) {
+    *reinterpret_cast<float*>(Ob + at) = val.x;
+    *reinterpret_cast<float*>(Ob + at + 4u * RL) = val.y;
+  };
+#pragma unroll
+  for (int k2 = 0; k2 < 30; ++k2) {
+    const int c = signed_residue(391 * k2);
+    if (c > 0 && c < HALF) continue;                        // (compile time) row 0 must not store these: below
+    const unsigned jl_b = sad(sad(ap, 4u * (unsigned)(HALF - c)), 4u * HALF, row_b);
+    put(jl_b, v[k2]);
+    if (!HALF_ROWS && k2 != 15) put(mirror_b - jl_b, v[k2]);
+  }
+  if (k1 != 0) {
+#pragma unroll
+    for (int k2 = 0; k2 < 30; ++k2) {
+      const int c = signed_residue(391 * k2);
+      if (!(c > 0 && c < HALF) && k2 != 15) continue;
+      const unsigned jl_b = sad(sad(ap, 4u * (unsigned)(HALF - c)), 4u * HALF, row_b);
+      if (k2 != 15) put(jl_b, v[k2]);
+      if (!HALF_ROWS) put(mirror_b - jl_b, v[k2]);
+    }
+  }
+}
+
 }  // namespace pfa
 
 // KIND / ACT / MODE are kernel ARGUMENTS, not template parameters: the three tap syntheses of a step (all-pass, dynamic
@@ -495,29 +561,21 @@ __device__ __forceinline__ void taps_pfa510_body(const TapsJobs& jobs, const Exc
       // an even response (sym): only the results at taps j <= N/2 are used -- tap N - j is the same number.  (Row k1 = 0 holds
       // both j and N - j of its own; they agree to rounding only, so the one at j <= N/2 serves both and a response comes out
       // EXACTLY even whichever layout stores it.)  half: the staging rows hold the NB taps j <= N/2.
-      const int rl = half ? NB : NT;
-      float* oa = O + (2 * t) * rl;
-      float* ob = oa + rl;
-      const int base = (120 * k1 + HALF) % NT;
+      if (!sym) {
+        float* oa = O + (2 * t) * NT;                       // whole rows (half rows are an even response's: launch_taps_pfa510)
+        float* ob = oa + NT;
+        const int base = (120 * k1 + HALF) % NT;
 #pragma unroll
-      for (int k2 = 0; k2 < 30; ++k2) {
-        int j = base + (391 * k2) % NT;                     // the second term is a compile-time constant
-        if (j >= NT) j -= NT;
-        if (!sym) {
+        for (int k2 = 0; k2 < 30; ++k2) {
+          int j = base + (391 * k2) % NT;                   // the second term is a compile-time constant
+          if (j >= NT) j -= NT;
           oa[j] = v[k2].x;
           ob[j] = v[k2].y;
-        } else {
-          const int jm = j ? NT - j : 0;                    // z[-m] = z[m]: tap 510 - j
-          const int jl = j <= HALF ? j : jm;                // the one of the two at or below N/2
-          if (k1 != 0 || j <= HALF) {
-            oa[jl] = v[k2].x;
-            ob[jl] = v[k2].y;
-            if (!half) {
-              const int jh = NT - jl;                       // its mirror image (jl = 0 has none; jl = N/2 is its own)
-              if (jl != 0) { oa[jh] = v[k2].x; ob[jh] = v[k2].y; }
-            }
-          }
         }
+      } else if (half) {                                    // workgroup-uniform
+        store_even_rows<true>(O, t, k1, v);
+      } else {
+        store_even_rows<false>(O, t, k1, v);
       }
     }
   }
