@@ -10,6 +10,7 @@ Sins/CombSub forward pass of yxlllc/DDSP-SVC).
   conformer -- the control network's ConformerConvModule / conv-only CFNEncoderLayer: one fused f32 MFMA launch per module
   attention -- PCmer's performer attention (FastAttention / SelfAttention): two fused f32 MFMA launches per call
   wavenet   -- the diffusion denoiser's WaveNet ResidualBlock: one fused f32 MFMA launch per layer, the skip sum in place
+  naive_v2  -- the reflow / diffusion-fast denoiser's NaiveV2DiffLayer: two fused f32 MFMA launches per layer
   loss      -- ddsp/loss.py SSSLoss / RSSLoss (the STFT of any size below 2049 as an in-kernel chirp-z transform, the loss and
                its gradient in the same kernels; torch.stft only above that)
   resample  -- torchaudio's sinc resampling (functional.resample / transforms.Resample) as an f32 MFMA GEMM
@@ -17,6 +18,6 @@ Sins/CombSub forward pass of yxlllc/DDSP-SVC).
   features  -- the frame features of the real-time path: volume, silence mask / gate, salience decode, F0 track
   sharding  -- utterance sharding across the GPUs of a node (+ optional RCCL gather)
 """
-from . import _ffi, attention, build, conformer, core, features, loss, mel, nsf_generator, nsf_source, resample, splice, synth, wavenet  # noqa: F401
+from . import _ffi, attention, build, conformer, core, features, loss, mel, naive_v2, nsf_generator, nsf_source, resample, splice, synth, wavenet  # noqa: F401
 
 __version__ = "0.1.0"

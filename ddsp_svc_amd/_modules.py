@@ -1,5 +1,5 @@
-"""What the reference-module hooks (``nsf_generator``, ``conformer``, ``mel``) share: the cache of packed weight tables and the
-predicates their eligibility checks are made of.
+"""What the reference-module hooks (``nsf_generator``, ``conformer``, ``mel``) share: the cache of packed weight tables, the
+predicates their eligibility checks are made of and the rule of the per-stream workspaces (``attention``, ``naive_v2``).
 
 The cache rule: a table is found again by the device, the kind of kernel, the shape integers and the ``data_ptr`` of every
 parameter tensor; it is a hit only while every tensor's ``_version`` is the one it was packed at (an in-place write packs
@@ -38,6 +38,33 @@ def clear_packed():
     """drop every cached table"""
     with _LOCK:
         _PACKED.clear()
+
+
+_WS_LOCK = threading.Lock()
+
+
+def stream_workspace(cache, floats, x, keep):
+    """the float32 buffer of at least ``floats`` elements that ``cache`` (a module's own ``OrderedDict``) holds for ``x``'s device
+    and the caller's current stream there: never shared between streams, grown on demand, the ``keep`` most recently used kept.
+    During a graph capture the cache is neither read nor grown: the buffer then comes from the graph's pool and belongs to the
+    graph, which holds no address that a later growth or ``drop_workspaces`` frees."""
+    if x.is_cuda and torch.cuda.is_current_stream_capturing():
+        return torch.empty(floats, dtype=torch.float32, device=x.device)
+    key = (str(x.device), _ffi.stream_of(x))
+    with _WS_LOCK:
+        ws = cache.get(key)
+        if ws is None or ws.numel() < floats:
+            ws = cache[key] = torch.empty(floats, dtype=torch.float32, device=x.device)
+            while len(cache) > keep:
+                cache.popitem(last=False)
+        cache.move_to_end(key)
+    return ws
+
+
+def drop_workspaces(cache):
+    """empty a ``stream_workspace`` cache"""
+    with _WS_LOCK:
+        cache.clear()
 
 
 def on_device(x, dim=None):

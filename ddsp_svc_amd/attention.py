@@ -22,13 +22,12 @@ frames B N below which the same-GPU torch chain was measured faster (tools/atten
 """
 import collections
 import sys
-import threading
 
 import torch
 import torch.nn.functional as F
 
 from . import _ffi
-from ._modules import needs_grad, on_device, packed_table, plain, torch_faster
+from ._modules import drop_workspaces, needs_grad, on_device, packed_table, plain, stream_workspace, torch_faster
 from ._patching import park, unpark
 
 DIM_HEAD = 64
@@ -41,7 +40,6 @@ ATTN_TORCH_FASTER = {}
 CALLS = {"hip": 0, "reference": 0}
 PACKS = {"count": 0}                                   # tables built: projections packed and q/k/v weights concatenated
 
-_LOCK = threading.Lock()
 _WS = collections.OrderedDict()                        # (device, stream) -> the key partials' buffer
 _WS_MAX = 16
 
@@ -57,26 +55,14 @@ def default_chunks(B, H, N):
 
 
 def _workspace(nbytes, x):
-    """the key partials' buffer of ``x``'s device and the caller's stream there, by ``nsf_generator._workspace``'s rule: never
+    """the key partials' buffer of ``x``'s device and the caller's stream there, by ``_modules.stream_workspace``'s rule: never
     shared between streams, and during a graph capture neither read nor grown (the buffer then belongs to the graph)"""
-    n = max((nbytes + 3) // 4, 4)
-    if x.is_cuda and torch.cuda.is_current_stream_capturing():
-        return torch.empty(n, dtype=torch.float32, device=x.device)
-    key = (str(x.device), _ffi.stream_of(x))
-    with _LOCK:
-        ws = _WS.get(key)
-        if ws is None or ws.numel() < n:
-            ws = _WS[key] = torch.empty(n, dtype=torch.float32, device=x.device)
-            while len(_WS) > _WS_MAX:
-                _WS.popitem(last=False)
-        _WS.move_to_end(key)
-    return ws
+    return stream_workspace(_WS, max((nbytes + 3) // 4, 4), x, _WS_MAX)
 
 
 def release_workspace():
     """drop the cached key-partial buffers of every device and stream"""
-    with _LOCK:
-        _WS.clear()
+    drop_workspaces(_WS)
 
 
 def _pack(dims, tensors):

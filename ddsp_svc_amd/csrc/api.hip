@@ -11,6 +11,7 @@
 #include "conformer_conv.h"
 #include "wavenet_layer.h"
 #include "performer_attention.h"
+#include "naive_v2_layer.h"
 #include <atomic>
 #include <stdio.h>
 #include <mutex>
@@ -1600,6 +1601,43 @@ int ddsp_hip_performer_attention(const float* q, const float* k, const float* v,
   if (table_bytes < performer_pack_bytes(d, m) || ws_bytes < performer_ws_bytes(B, H, N, chunks)) return DDSP_HIP_EWS;
   launch_performer_attention(q, k, v, out, strides, static_cast<const float*>(table), static_cast<float*>(ws), B, H, N,
                              normalize ? 1 : 0, chunks, S(stream));
+  return finish();
+}
+
+int ddsp_hip_naive_v2_layer_tile(int D, int Hc, int which) {
+  if (!nv2::shape_ok(D, Hc) || (which != 0 && which != 1)) return 0;
+  return which == 0 ? nv2::kTA : nv2::kTB;
+}
+
+size_t ddsp_hip_naive_v2_layer_pack_bytes(int D, int Hc) { return naive_v2_layer_pack_bytes(D, Hc); }
+
+int ddsp_hip_naive_v2_layer_pack(const float* wc, const float* bc, const float* w1, const float* b1, const float* wd,
+                                 const float* bd, const float* w2, const float* b2, int D, int Hc, void* packed,
+                                 size_t packed_bytes) {
+  if (!wc || !bc || !w1 || !b1 || !wd || !bd || !w2 || !b2 || !packed) return DDSP_HIP_EINVAL;
+  const size_t need = naive_v2_layer_pack_bytes(D, Hc);
+  if (need == 0) return DDSP_HIP_ESHAPE;
+  if (packed_bytes < need) return DDSP_HIP_EWS;
+  naive_v2_layer_pack(wc, bc, w1, b1, wd, bd, w2, b2, D, Hc, static_cast<float*>(packed));
+  return 0;
+}
+
+size_t ddsp_hip_naive_v2_layer_workspace_bytes(long B, long L, int D) {
+  if (B < 0 || L < 1 || L > (1L << 30) || !nv2::shape_ok(D, 128)) return 0;   // g is 2 D wide whatever Hc is: the one Hc built
+  return naive_v2_layer_ws_bytes(B, L, D);
+}
+
+int ddsp_hip_naive_v2_layer(const float* x, const float* cond, const float* d, float* y, const void* packed, size_t packed_bytes,
+                            void* ws, size_t ws_bytes, int B, long L, int D, int Hc, void* stream) {
+  if (B < 0 || L < 1) return DDSP_HIP_EINVAL;
+  if (!nv2::shape_ok(D, Hc) || L > (1L << 30)) return DDSP_HIP_ESHAPE;
+  if (B == 0) return 0;
+  if (!x || !cond || !d || !y || !packed || !ws || y == x || y == cond) return DDSP_HIP_EINVAL;
+  if (packed_bytes < naive_v2_layer_pack_bytes(D, Hc) || ws_bytes < naive_v2_layer_ws_bytes(B, L, D)) return DDSP_HIP_EWS;
+  if ((reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(d) & 15) || (reinterpret_cast<uintptr_t>(y) & 15) ||
+      (reinterpret_cast<uintptr_t>(packed) & 15) || (reinterpret_cast<uintptr_t>(cond) & 3) || (reinterpret_cast<uintptr_t>(ws) & 3))
+    return DDSP_HIP_EINVAL;                            // the kernels read x, d and the biases and write y 4 channels at a time
+  launch_naive_v2_layer(x, cond, d, y, static_cast<const float*>(packed), static_cast<float*>(ws), B, L, D, Hc, S(stream));
   return finish();
 }
 

@@ -14,7 +14,7 @@
  *     T = F*hop; control tensors take a row stride `ld` (floats between consecutive frames) so
  *     the torch.split views of Unit2Control's output can be passed without a copy;
  *   - more than 65 535 utterances in one call (a grid's limit in y and z): ddsp_hip_resblock1, ddsp_hip_upsample_stage,
- *     ddsp_hip_output_head, ddsp_hip_conformer_conv, ddsp_hip_wavenet_layer, ddsp_hip_resample and ddsp_hip_mel_shifted_spectrogram split the batch into launches of 65 535; ddsp_hip_fast_source and
+ *     ddsp_hip_output_head, ddsp_hip_conformer_conv, ddsp_hip_wavenet_layer, ddsp_hip_naive_v2_layer, ddsp_hip_resample and ddsp_hip_mel_shifted_spectrogram split the batch into launches of 65 535; ddsp_hip_fast_source and
  *     ddsp_hip_combsubsuperfast_synth run their exciter on a flat grid then; ddsp_hip_sine_source(_drawn),
  *     ddsp_hip_spectral_loss(_backward), ddsp_hip_stft_loss(_backward), ddsp_hip_mel_spectrogram_backward,
  *     ddsp_hip_sola_splice, ddsp_hip_volume, ddsp_hip_gate, ddsp_hip_pool1d, ddsp_hip_fft_convolve with
@@ -653,6 +653,34 @@ size_t ddsp_hip_performer_workspace_bytes(long B, int H, long N, int chunks);
 int ddsp_hip_performer_attention(const float* q, const float* k, const float* v, float* out, const long* strides,
                                  const void* table, size_t table_bytes, void* ws, size_t ws_bytes, long B, int H, long N, int d,
                                  int m, int normalize, int chunks, void* stream);
+
+/* The layer of the reflow / diffusion-fast denoiser (reflow/naive_v2_diff.py:81-98, NaiveV2DiffLayer in its default form: no
+ * attention, not wavenet_like, a conv module without LayerNorm), csrc/naive_v2_layer.h.  As above, these entry points came after
+ * version 165 without a version step.
+ *   x' = x + d + Conv1d(Hc, D, 1)(cond);  g = glu(Conv1d(D, 4 D, 1)(x'));  h = silu(Conv1d(2 D, 2 D, 31, padding 15, groups 2 D)(g))
+ *   y  = x + Conv1d(2 D, D, 1)(h)
+ * over x, y [B, L, D], cond [B, L, Hc] (a frame's channels contiguous) and d [B, D] (the layer's projection of the step
+ * embedding), contiguous float32; glu = rows [0, 2 D) times the sigmoid of rows [2 D, 4 D); the depthwise convolution is a
+ * cross-correlation that zero-pads g; the residual is the x that came in.  (D, Hc) = (512, 128) (DDSP_HIP_ESHAPE otherwise),
+ * forward only.
+ * ddsp_hip_naive_v2_layer_tile: frames per workgroup of the first launch (which = 0: 64) or the second (1: 112); 0 for a shape
+ * the kernels do not take or another which.
+ * ddsp_hip_naive_v2_layer_pack_bytes / _pack: HOST weights wc [D][Hc], bc [D], w1 [4 D][D], b1 [4 D], wd [2 D][31], bd [2 D],
+ * w2 [D][2 D], b2 [D] -> the table the kernels read, written to HOST memory (the caller copies it to the device once and keeps
+ * it).  0 bytes / DDSP_HIP_ESHAPE out of range, DDSP_HIP_EWS short.
+ * ddsp_hip_naive_v2_layer_workspace_bytes: B x 2 D x L floats, where the first launch leaves g for the second; 0 for arguments
+ * the call below refuses.
+ * ddsp_hip_naive_v2_layer: 1 <= L <= 2^30 (DDSP_HIP_EINVAL / DDSP_HIP_ESHAPE); x, d, y and packed 16-byte aligned; y must be
+ * neither x nor cond (DDSP_HIP_EINVAL); a short table or workspace is DDSP_HIP_EWS; B = 0 is a no-op.  Two launches on the
+ * stream (per 65 535 utterances), f32 MFMA, 128.5 KB and 36 KB of LDS per workgroup.  No allocation, no synchronisation. */
+int ddsp_hip_naive_v2_layer_tile(int D, int Hc, int which);
+size_t ddsp_hip_naive_v2_layer_pack_bytes(int D, int Hc);
+int ddsp_hip_naive_v2_layer_pack(const float* wc, const float* bc, const float* w1, const float* b1, const float* wd,
+                                 const float* bd, const float* w2, const float* b2, int D, int Hc, void* packed,
+                                 size_t packed_bytes);
+size_t ddsp_hip_naive_v2_layer_workspace_bytes(long B, long L, int D);
+int ddsp_hip_naive_v2_layer(const float* x, const float* cond, const float* d, float* y, const void* packed, size_t packed_bytes,
+                            void* ws, size_t ws_bytes, int B, long L, int D, int Hc, void* stream);
 
 #ifdef __cplusplus
 }
