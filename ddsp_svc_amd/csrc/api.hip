@@ -12,6 +12,7 @@
 #include "wavenet_layer.h"
 #include "performer_attention.h"
 #include "naive_v2_layer.h"
+#include "naive_v2_split.h"
 #include <atomic>
 #include <stdio.h>
 #include <mutex>
@@ -1638,6 +1639,27 @@ int ddsp_hip_naive_v2_layer(const float* x, const float* cond, const float* d, f
       (reinterpret_cast<uintptr_t>(packed) & 15) || (reinterpret_cast<uintptr_t>(cond) & 3) || (reinterpret_cast<uintptr_t>(ws) & 3))
     return DDSP_HIP_EINVAL;                            // the kernels read x, d and the biases and write y 4 channels at a time
   launch_naive_v2_layer(x, cond, d, y, static_cast<const float*>(packed), static_cast<float*>(ws), B, L, D, Hc, S(stream));
+  return finish();
+}
+
+int ddsp_hip_naive_v2_layer_split_tile(int D, int Hc) { return nv2::shape_ok(D, Hc) ? nv2s::kT : 0; }
+
+size_t ddsp_hip_naive_v2_layer_split_workspace_bytes(long B, long L, int D) {
+  if (B < 0 || L < 1 || L > (1L << 30) || !nv2::shape_ok(D, 128) || !nv2s::in_range(B, L)) return 0;
+  return naive_v2_split_ws_bytes(B, L, D);
+}
+
+int ddsp_hip_naive_v2_layer_split(const float* x, const float* cond, const float* d, float* y, const void* packed,
+                                  size_t packed_bytes, void* ws, size_t ws_bytes, int B, long L, int D, int Hc, void* stream) {
+  if (B < 0 || L < 1) return DDSP_HIP_EINVAL;
+  if (!nv2::shape_ok(D, Hc) || L > (1L << 30) || !nv2s::in_range(B, L)) return DDSP_HIP_ESHAPE;
+  if (B == 0) return 0;
+  if (!x || !cond || !d || !y || !packed || !ws || y == x || y == cond) return DDSP_HIP_EINVAL;
+  if (packed_bytes < naive_v2_layer_pack_bytes(D, Hc) || ws_bytes < naive_v2_split_ws_bytes(B, L, D)) return DDSP_HIP_EWS;
+  if ((reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(d) & 15) || (reinterpret_cast<uintptr_t>(y) & 15) ||
+      (reinterpret_cast<uintptr_t>(packed) & 15) || (reinterpret_cast<uintptr_t>(cond) & 3) || (reinterpret_cast<uintptr_t>(ws) & 15))
+    return DDSP_HIP_EINVAL;                            // x' goes through the workspace 4 channels at a time as well
+  launch_naive_v2_split(x, cond, d, y, static_cast<const float*>(packed), static_cast<float*>(ws), B, L, D, Hc, S(stream));
   return finish();
 }
 

@@ -5,6 +5,7 @@ and the residual -- with the GLU's output handed over through a workspace.  f32 
 
   tile                        ``(t_A, t_B)``: frames per workgroup of the two launches (``ddsp_hip_naive_v2_layer_tile``)
   diff_layer                  the functional form: ``x [B, L, D]``, ``cond [B, L, Hc]``, ``d [B, D]``, the eight weight tensors
+  choose_form                 ``"split"``, ``"tiled"`` or None (torch) for a size, from the two measured tables
   diff_stack                  all layers of a denoiser: one matmul for every layer's step projection, one launch pair per layer
   layer_forward / net_forward the dispatchers bound as ``NaiveV2DiffLayer.forward`` / ``NaiveV2Diff.forward``
   patch_reference_naive_v2    rebinds those two in whichever of the two reference modules import; opt-in
@@ -18,6 +19,11 @@ without hooks, float32 tensors on the GPU, no gradient needed, autocast off, (D,
 module's own forward.  ``LAYER_TORCH_FASTER`` maps D to the number of frames B L below which the same-GPU torch chain was
 measured faster (tools/naive_v2_bench.py); None: at every size, which is also what a D without a committed
 measurement gets.
+
+The layer has a second form, csrc/naive_v2_split.h (``form="split"``): the same sums in the same order, hence the same bits, with
+a frame tile of 16 and the channels split over workgroups, four launches, for calls of a few hundred frames (``B ceil(L / 16) <=
+4096``).  ``SPLIT_BELOW`` maps D to the number of frames below which it was measured the fastest of the three, and
+``choose_form`` is the one place where the hook decides between the split form, the tiled form and torch.
 """
 import collections
 import threading
@@ -38,8 +44,17 @@ TAPS = 31
 # (x0.23, x0.23, x0.87), the kernels at 32 x 862 = 27 584, the smallest size at which they were seen to win (x1.62), and at
 # 64 x 862 (x1.68).
 LAYER_TORCH_FASTER = {512: 27584}
-# dispatch counters (tests and tools read them): layer calls; separate from conformer.CALLS and wavenet.CALLS
-CALLS = {"hip": 0, "reference": 0}
+# D -> the number of frames B L below which the channel-split form (csrc/naive_v2_split.h) was MEASURED faster than both the
+# torch chain and the tiled form (tools/naive_v2_bench.py --mode split, profiles/naive_v2_split_latency.json): the smallest
+# measured size at which it was not the fastest of the three; no entry where it is not the fastest at 1 x 100.  On one MI355X it
+# was the fastest at all five measured sizes -- 1 x 100, 1 x 203, 4 x 203, 1 x 862 (x1.88, x1.67, x1.32, x1.51 over torch) and, by
+# 3 %, 48 x 172 = 8 256 frames --, so the bound is one past the largest of them: nothing above it was measured.
+SPLIT_BELOW = {512: 8257}
+SPLIT_MAX_TILES = 4096                                 # the split form takes B ceil(L / 16) up to here
+FORMS = ("tiled", "split")
+# dispatch counters (tests and tools read them): layer calls ("hip": on the kernels in either form, "split": those of them that
+# took the split form); separate from conformer.CALLS and wavenet.CALLS
+CALLS = {"hip": 0, "reference": 0, "split": 0}
 PACKS = {"count": 0}                                   # weight tables built (a cache hit does not count)
 _LOCK = threading.Lock()                               # guards _STACKED
 _WS = collections.OrderedDict()                        # (device, stream) -> the buffer the GLU's output passes through
@@ -54,11 +69,31 @@ def tile(D, Hc):
     return int(lib.ddsp_hip_naive_v2_layer_tile(int(D), int(Hc), 0)), int(lib.ddsp_hip_naive_v2_layer_tile(int(D), int(Hc), 1))
 
 
-def _workspace(B, L, D, x):
-    """the buffer the GLU's output passes through, for ``x``'s device and the caller's stream there
-    (``_modules.stream_workspace``'s rule)"""
-    nbytes = int(_ffi.lib().ddsp_hip_naive_v2_layer_workspace_bytes(B, L, D))
-    return stream_workspace(_WS, max(nbytes // 4, 4), x, _WS_MAX)
+def split_tile(D, Hc):
+    """frames per workgroup of the split form; 0 for a shape the kernels do not take"""
+    return int(_ffi.lib().ddsp_hip_naive_v2_layer_split_tile(int(D), int(Hc)))
+
+
+def split_in_range(B, L):
+    """the split form takes ``B ceil(L / 16)`` tiles up to ``SPLIT_MAX_TILES``"""
+    return B * -(-L // 16) <= SPLIT_MAX_TILES
+
+
+def choose_form(D, B, L):
+    """where the hook sends a layer call of ``B x L`` frames: ``"split"`` within the split form's range below the measured
+    ``SPLIT_BELOW[D]``, else ``"tiled"`` unless ``LAYER_TORCH_FASTER`` gives the size to torch, else None (the torch chain).
+    The two forms give the same bits, so the choice never shows in a result."""
+    if D in SPLIT_BELOW and split_in_range(B, L) and B * L < SPLIT_BELOW[D]:
+        return "split"
+    return None if torch_faster(LAYER_TORCH_FASTER, D, B * L) else "tiled"
+
+
+def _workspace(B, L, D, x, form="tiled"):
+    """the buffer the intermediates pass through (tiled: the GLU's output; split: x', the GLU's output and the stencil's), for
+    ``x``'s device and the caller's stream there (``_modules.stream_workspace``'s rule)"""
+    lib = _ffi.lib()
+    size = lib.ddsp_hip_naive_v2_layer_split_workspace_bytes if form == "split" else lib.ddsp_hip_naive_v2_layer_workspace_bytes
+    return stream_workspace(_WS, max(int(size(B, L, D)) // 4, 4), x, _WS_MAX)
 
 
 def release_workspace():
@@ -89,13 +124,16 @@ def _check_weights(weights, D, Hc):
                          "[D, 2 D, 1], [D]")
 
 
-def diff_layer(x, cond, d, weights, out=None, ws=None):
+def diff_layer(x, cond, d, weights, out=None, ws=None, form="tiled"):
     """One layer on the HIP kernels: ``x [B, L, D]``, ``cond [B, L, Hc]`` (a frame's channels contiguous), ``d [B, D]`` (the
     layer's projection of the step embedding), ``weights = (wc [D, Hc, 1], bc [D], w1 [4 D, D, 1], b1 [4 D], wd [2 D, 1, 31],
     bd [2 D], w2 [D, 2 D, 1], b2 [D])``, all float32.  Returns ``x + conv_module(x + d + Wc cond + bc)`` in ``out``, which must not
-    be ``x``.  ``ws``: a float32 buffer of at least ``B 2 D L`` elements for the GLU's output, instead of the cached one of the
-    caller's stream.  No synchronisation; once the weight table and the workspace exist the only allocation is the result (when
-    ``out`` is None), so a call can be captured in a graph (a capture without ``ws`` takes a workspace from the graph's pool)."""
+    be ``x``.  ``form``: ``"tiled"`` (csrc/naive_v2_layer.h, two launches) or ``"split"`` (csrc/naive_v2_split.h, four launches with
+    a frame tile of 16 for calls of a few hundred frames, ``B ceil(L / 16) <= 4096``, ValueError beyond); both give the same bits.
+    ``ws``: a float32 buffer of at least ``B 2 D L`` (tiled) or ``5 B L D`` (split) elements for the intermediates, instead of the
+    cached one of the caller's stream.  No synchronisation; once the weight table and the workspace exist the only allocation is
+    the result (when ``out`` is None), so a call can be captured in a graph (a capture without ``ws`` takes a workspace from the
+    graph's pool)."""
     _ffi.check_device(x, cond, d, out)
     if any(not isinstance(t, torch.Tensor) or t.dtype != torch.float32 for t in (x, cond, d)) or x.dim() != 3 or cond.dim() != 3:
         raise ValueError("diff_layer: x [B, L, D], cond [B, L, Hc] and d [B, D] must be float32 tensors")
@@ -108,6 +146,10 @@ def diff_layer(x, cond, d, weights, out=None, ws=None):
     _check_weights(weights, D, Hc)
     if L < 1:
         raise ValueError("diff_layer: L must be positive")
+    if form not in FORMS:
+        raise ValueError("diff_layer: form must be 'tiled' or 'split'")
+    if form == "split" and not split_in_range(B, L):
+        raise ValueError("diff_layer: the split form takes B ceil(L / 16) <= %d tiles" % SPLIT_MAX_TILES)
     if out is x or out is cond:
         raise ValueError("diff_layer: out must be neither x nor cond")
     x, cond, d = x.contiguous(), cond.contiguous(), d.contiguous()
@@ -119,12 +161,15 @@ def diff_layer(x, cond, d, weights, out=None, ws=None):
     lib = _ffi.lib()
     table = packed_table("naive_v2", (D, Hc), list(weights), x.device, _pack)
     if ws is None:
-        ws = _workspace(B, L, D, x)
+        ws = _workspace(B, L, D, x, form)
     elif ws.dtype != torch.float32 or not ws.is_contiguous() or ws.device != x.device:
         raise ValueError("diff_layer: ws must be a contiguous float32 tensor on x's device")
     CALLS["hip"] += 1
-    _ffi.check(lib.ddsp_hip_naive_v2_layer(x.data_ptr(), cond.data_ptr(), d.data_ptr(), y.data_ptr(), table.data_ptr(),
-                                           table.numel() * 4, ws.data_ptr(), ws.numel() * 4, B, L, D, Hc, _ffi.stream_of(x)))
+    if form == "split":
+        CALLS["split"] += 1
+    entry = lib.ddsp_hip_naive_v2_layer_split if form == "split" else lib.ddsp_hip_naive_v2_layer
+    _ffi.check(entry(x.data_ptr(), cond.data_ptr(), d.data_ptr(), y.data_ptr(), table.data_ptr(), table.numel() * 4, ws.data_ptr(),
+                     ws.numel() * 4, B, L, D, Hc, _ffi.stream_of(x)))
     return y
 
 
@@ -147,11 +192,11 @@ def _stacked_projection(projs):
     return W, b
 
 
-def diff_stack(x, cond, s, layers):
+def diff_stack(x, cond, s, layers, form="tiled"):
     """The layers of a denoiser: ``x [B, L, D]``, ``cond [B, L, Hc]``, ``s [B, D]`` (the step embedding), ``layers`` a list of
     ``(weights, (wp [D, D, 1], bp [D]))``.  The step projections of all layers are ONE matmul; then one launch pair per layer, x
     handed over through two buffers (the caller's x is never written), one workspace for all layers (in a graph capture as
-    well).  Returns x after the last layer."""
+    well).  ``form`` as in ``diff_layer``, for every layer.  Returns x after the last layer."""
     if not layers:
         raise ValueError("diff_stack: no layers")
     if any(not isinstance(t, torch.Tensor) or t.dtype != torch.float32 for t in (x, s)) or x.dim() != 3 or x.shape[1] < 1:
@@ -160,17 +205,19 @@ def diff_stack(x, cond, s, layers):
     n = len(layers)
     if tuple(s.shape) != (B, D) or any(tuple(p[0].shape) != (D, D, 1) or tuple(p[1].shape) != (D,) for _, p in layers):
         raise ValueError("diff_stack: s must be [B, D] and every step projection ([D, D, 1], [D])")
+    if form not in FORMS or (form == "split" and not split_in_range(B, L)):
+        raise ValueError("diff_stack: form must be 'tiled' or 'split', the latter with B ceil(L / 16) <= %d" % SPLIT_MAX_TILES)
     _ffi.check_device(x, cond, s)
     W, b = _stacked_projection([p for _, p in layers])
     d = torch.addmm(b, s, W.t()).view(B, n, D).transpose(0, 1).contiguous()              # [n, B, D]
     cond = cond.contiguous()
     bufs = (torch.empty_like(x, memory_format=torch.contiguous_format),
             torch.empty_like(x, memory_format=torch.contiguous_format) if n > 1 else None)
-    ws = _workspace(B, L, D, x) if B else None
+    ws = _workspace(B, L, D, x, form) if B else None
     src = x
     for i, (weights, _) in enumerate(layers):
         dst = bufs[(n - 1 - i) % 2]                    # the last layer writes the first buffer
-        diff_layer(src, cond, d[i], weights, out=dst, ws=ws)
+        diff_layer(src, cond, d[i], weights, out=dst, ws=ws, form=form)
         src = dst
     return src
 
@@ -207,7 +254,7 @@ def _layer_spec(layer):
 
 def layer_eligible(layer, x, cond, step):
     """the ``(weights, (wp, bp))`` to run ``layer`` on the reference's ``x [B, D, L]``, ``cond [B, Hc, L]``, ``step [B, D, 1]``
-    with the HIP kernels, or None: the layer's own forward"""
+    with the HIP kernels (in the form ``choose_form`` names for the size), or None: the layer's own forward"""
     if not on_device(x, 3) or not on_device(cond, 3) or not on_device(step, 3) or x.shape[2] < 1:
         return None
     if torch.is_autocast_enabled(x.device.type):
@@ -223,7 +270,7 @@ def layer_eligible(layer, x, cond, step):
     flat = list(weights) + list(proj)
     if any(t.device != x.device for t in flat + [cond, step]) or needs_grad([x, cond, step] + flat):
         return None
-    if torch_faster(LAYER_TORCH_FASTER, D, B * L):
+    if choose_form(D, B, L) is None:
         return None
     return spec
 
@@ -246,7 +293,8 @@ def layer_forward(layer, x, condition=None, diffusion_step=None):
         return _reference_layer_forward(layer, x, condition, diffusion_step)
     weights, (wp, bp) = spec
     d = torch.addmm(bp, diffusion_step[:, :, 0], wp[:, :, 0].t())
-    return diff_layer(x.transpose(1, 2), condition.transpose(1, 2), d, weights).transpose(1, 2)
+    form = choose_form(x.shape[1], x.shape[0], x.shape[2])
+    return diff_layer(x.transpose(1, 2), condition.transpose(1, 2), d, weights, form=form).transpose(1, 2)
 
 
 def _reference_net_forward(net, spec, diffusion_step, cond):
@@ -268,7 +316,7 @@ def _stack_candidate(net, spec, cond):
     specs = [_layer_spec(layer) for layer in layers]
     if any(sp is None for sp in specs) or needs_grad([spec, cond] + list(net.parameters())):
         return False
-    return not torch_faster(LAYER_TORCH_FASTER, specs[0][0][2].shape[1], spec.shape[0] * spec.shape[-1])
+    return choose_form(specs[0][0][2].shape[1], spec.shape[0], spec.shape[-1]) is not None
 
 
 def net_forward(net, spec, diffusion_step, cond):
@@ -284,7 +332,8 @@ def net_forward(net, spec, diffusion_step, cond):
         condition = net.conditioner_projection(cond)
         specs = [layer_eligible(layer, x, condition, step) for layer in net.residual_layers]
         if all(sp is not None for sp in specs):
-            y = diff_stack(x.transpose(1, 2), condition.transpose(1, 2), step.select(2, 0), specs)
+            form = choose_form(x.shape[1], x.shape[0], x.shape[2])
+            y = diff_stack(x.transpose(1, 2), condition.transpose(1, 2), step.select(2, 0), specs, form)
             out = net.output_projection(y.transpose(1, 2))
             return out.unsqueeze(1) if spec.dim() == 4 else out
     return _reference_net_forward(net, spec, diffusion_step, cond)

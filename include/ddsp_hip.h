@@ -682,6 +682,21 @@ size_t ddsp_hip_naive_v2_layer_workspace_bytes(long B, long L, int D);
 int ddsp_hip_naive_v2_layer(const float* x, const float* cond, const float* d, float* y, const void* packed, size_t packed_bytes,
                             void* ws, size_t ws_bytes, int B, long L, int D, int Hc, void* stream);
 
+/* The same layer in its channel-split form, csrc/naive_v2_split.h, for calls of a few hundred frames: a frame tile of 16, the
+ * channels split over workgroups and waves, four plain launches on the stream (x', the GLU, the stencil, the output GEMM), every
+ * sum in the order of ddsp_hip_naive_v2_layer, so the two give the same bits.  It reads the table of ddsp_hip_naive_v2_layer_pack.
+ * As above, these entry points came after version 165 without a version step.
+ * ddsp_hip_naive_v2_layer_split_tile: frames per workgroup (16); 0 for a shape the kernels do not take.
+ * ddsp_hip_naive_v2_layer_split_workspace_bytes: 5 B L D floats (x' [B, L, D], g and h [B, 2 D, L]); 0 for arguments the call
+ * below refuses.
+ * ddsp_hip_naive_v2_layer_split: the arguments, checks and error codes of ddsp_hip_naive_v2_layer, and B ceil(L / 16) <= 4096
+ * (DDSP_HIP_ESHAPE beyond: the tiled form is for the rest); ws 16-byte aligned.  33 KB of LDS in the second launch.  No
+ * allocation, no synchronisation. */
+int ddsp_hip_naive_v2_layer_split_tile(int D, int Hc);
+size_t ddsp_hip_naive_v2_layer_split_workspace_bytes(long B, long L, int D);
+int ddsp_hip_naive_v2_layer_split(const float* x, const float* cond, const float* d, float* y, const void* packed,
+                                  size_t packed_bytes, void* ws, size_t ws_bytes, int B, long L, int D, int Hc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

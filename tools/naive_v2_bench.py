@@ -8,6 +8,10 @@ GPU in the same process with the same weights, the two alternated step by step.
                around each call  -> profiles/naive_v2_throughput.json
   latency      the same two at B x L = 1 x 100 (the streaming shape) and 1 x 203 (the GUI's 2.35 s window), call to result: a
                host clock around the call and a device synchronise  -> profiles/naive_v2_latency.json
+  split        three sides -- the torch chain, the tiled form and the channel-split form (csrc/naive_v2_split.h) -- at B x L =
+               1 x 100, 1 x 203, 1 x 862, 4 x 203 and 48 x 172, one layer and the 6-layer stack, alternated step by step, call
+               to result  -> profiles/naive_v2_split_latency.json; ``split_below`` there is what naive_v2.SPLIT_BELOW is
+               filled from.  Not part of ``both``: it leaves the two files above as they are.
 
 Each pair runs --steps alternated steps and is timed over the LAST --tail of them: the first ones run on a clock that is still
 settling (EXPERIMENTS.md 6.1), so a ramp of matrix products runs first.  The achieved fraction of the 155 TF f32 MFMA peak is
@@ -33,7 +37,8 @@ import torch.nn.functional as F
 D, HC = 512, 128
 LAYERS = 6
 PEAK_TFLOPS = 155.0                                    # measured f32 MFMA peak of one MI355X
-SHAPES = {"throughput": ((64, 862), (32, 862), (48, 172)), "latency": ((1, 100), (1, 203))}
+SHAPES = {"throughput": ((64, 862), (32, 862), (48, 172)), "latency": ((1, 100), (1, 203)),
+          "split": ((1, 100), (1, 203), (1, 862), (4, 203), (48, 172))}
 STEP_LIMIT_S = 300                                     # per child
 
 
@@ -90,6 +95,70 @@ def compare(hip, ref, steps, tail, events):
     (hm, hl, hh), (tm, tl, tu) = q(th), q(tt)
     return {"hip_ms": hm, "hip_ms_p10_p90": [hl, hh], "torch_ms": tm, "torch_ms_p10_p90": [tl, tu], "torch_over_hip": tm / hm,
             "hip_ms_first_steps": float(np.median(th[:5])) * 1e3, "max_abs_diff_over_rms": diff}
+
+
+def compare3(sides, steps, tail):
+    """alternated: torch, tiled, split, torch, ...; call to result; the median and spread of each over the last ``tail`` steps.
+    ``sides``: name -> callable returning [B, L, D]."""
+    out = {k: fn() for k, fn in sides.items()}
+    torch.cuda.synchronize()
+    r = {"split_equals_tiled": bool(torch.equal(out["split"], out["tiled"])),
+         "max_abs_diff_over_rms": float((out["split"] - out["torch"]).abs().max() / out["torch"].pow(2).mean().sqrt())}
+    del out
+    times = {k: [] for k in sides}
+    for _ in range(steps):
+        for k, fn in sides.items():
+            times[k].append(timed(fn, False))
+    for k, v in times.items():
+        m, lo, hi = [float(np.percentile(v[-tail:], p)) * 1e3 for p in (50, 10, 90)]
+        r[k + "_ms"], r[k + "_ms_p10_p90"] = m, [lo, hi]
+    r["fastest"] = min(sides, key=lambda k: r[k + "_ms"])
+    return r
+
+
+def run_split(steps, tail):
+    from ddsp_svc_amd import naive_v2 as NV
+    dev = torch.device("cuda:0")
+    layers = [make_layer(dev, 10 + i) for i in range(LAYERS)]
+    cases = []
+    ramp(dev)
+    with torch.no_grad():
+        for B, L in SHAPES["split"]:
+            gen = torch.Generator().manual_seed(B + L)
+            x, cond = torch.randn(B, L, D, generator=gen).to(dev), torch.randn(B, L, HC, generator=gen).to(dev)
+            s = torch.randn(B, D, generator=gen).to(dev)
+            xt, ct, st = x.transpose(1, 2).contiguous(), cond.transpose(1, 2).contiguous(), s.unsqueeze(-1)
+            out = torch.empty_like(x)
+            w0, (wp0, bp0) = layers[0]
+            layer = lambda form: lambda: NV.diff_layer(x, cond, torch.addmm(bp0, s, wp0[:, :, 0].t()), w0, out=out, form=form)
+            stack = lambda form: lambda: NV.diff_stack(x, cond, s, layers, form=form)
+            todo = (("layer", 1, steps, {"torch": lambda: torch_layer(xt, ct, st, layers[0]).transpose(1, 2),
+                                         "tiled": layer("tiled"), "split": layer("split")}),
+                    ("stack6", LAYERS, max(steps // 4, 8), {"torch": lambda: torch_stack(xt, ct, st, layers).transpose(1, 2),
+                                                            "tiled": stack("tiled"), "split": stack("split")}))
+            for name, n, k, sides in todo:
+                r = compare3(sides, k, min(tail, k))
+                r.update(case=name, D=D, B=B, L=L, frames=B * L, steps=k, launches_tiled=2 * n, launches_split=4 * n,
+                         tiles_split=B * -(-L // 16), workspace_bytes_split=5 * B * L * D * 4)
+                cases.append(r)
+                print(json.dumps(r), flush=True)
+            del x, cond, xt, ct, out
+            NV.release_workspace()
+            torch.cuda.empty_cache()
+    return {"tile": list(NV.tile(D, HC)), "tile_split": NV.split_tile(D, HC), "device": torch.cuda.get_device_name(0),
+            "torch": torch.__version__, "cases": cases}
+
+
+def split_below(cases):
+    """D -> the smallest measured size at which the split form was not the fastest of the three (one past the largest measured
+    size if it was the fastest at all of them); no entry if it is not the fastest at the smallest size"""
+    table = {}
+    for d in sorted({c["D"] for c in cases}):
+        mine = sorted((c["frames"], c["fastest"]) for c in cases if c["case"] == "layer" and c["D"] == d)
+        if mine and mine[0][1] == "split":
+            lost = [n for n, side in mine if side != "split"]
+            table[str(d)] = lost[0] if lost else mine[-1][0] + 1
+    return table
 
 
 def flops(B, L, layers, tiles):
@@ -152,7 +221,7 @@ def run(mode, steps, tail):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=("latency", "throughput", "both"), default="both")
+    ap.add_argument("--mode", choices=("latency", "throughput", "both", "split"), default="both")
     ap.add_argument("--steps", type=int, default=160)
     ap.add_argument("--tail", type=int, default=40)
     ap.add_argument("--out-dir", default=os.path.join(ROOT, "profiles"))
@@ -163,7 +232,8 @@ def main():
     if args.child:
         mode, path = args.child
         with open(path, "w") as f:
-            json.dump(run(mode, args.steps, min(args.tail, args.steps)), f)
+            tail = min(args.tail, args.steps)
+            json.dump(run_split(args.steps, tail) if mode == "split" else run(mode, args.steps, tail), f)
         return
     os.makedirs(args.out_dir, exist_ok=True)
     for mode in (("throughput", "latency") if args.mode == "both" else (args.mode,)):
@@ -171,7 +241,8 @@ def main():
         doc = {"mode": mode, "D": D, "Hc": HC, "layers_of_the_stack": LAYERS, "steps": args.steps,
                "timed_over_last": args.tail, "peak_tflops": PEAK_TFLOPS,
                "timing": "device events" if events else "host clock + synchronise", "cases": []}
-        part = os.path.join(args.out_dir, ".naive_v2_%s.part" % mode)
+        stem = "naive_v2_split_latency" if mode == "split" else "naive_v2_%s" % mode
+        part = os.path.join(args.out_dir, ".%s.part" % stem)
         cmd = ["timeout", "-k", "10", str(STEP_LIMIT_S), sys.executable, os.path.abspath(__file__), "--steps", str(args.steps),
                "--tail", str(args.tail), "--child", mode, part]
         code = subprocess.call(cmd)
@@ -182,8 +253,11 @@ def main():
         os.remove(part)
         doc["cases"] += got.pop("cases")
         doc.update(got)
-        doc["torch_faster_frames"] = sorted({c["frames"] for c in doc["cases"] if c["case"] == "layer" and c["torch_over_hip"] < 1.0})
-        path = os.path.join(args.out_dir, "naive_v2_%s.json" % mode)
+        if mode == "split":
+            doc["split_below"] = split_below(doc["cases"])
+        else:
+            doc["torch_faster_frames"] = sorted({c["frames"] for c in doc["cases"] if c["case"] == "layer" and c["torch_over_hip"] < 1.0})
+        path = os.path.join(args.out_dir, "%s.json" % stem)
         with open(path, "w") as f:
             f.write(json.dumps(doc, indent=1) + "\n")
         print("wrote", path, flush=True)
