@@ -9,7 +9,7 @@ Sins/CombSub forward pass of yxlllc/DDSP-SVC).
   nsf_generator -- nsf_hifigan.models.ResBlock1 and the per-stage block sum of Generator.forward: fused f32 MFMA conv pairs
   conformer -- the control network's ConformerConvModule / conv-only CFNEncoderLayer: one fused f32 MFMA launch per module
   attention -- PCmer's performer attention (FastAttention / SelfAttention): two fused f32 MFMA launches per call
-  wavenet   -- the diffusion denoiser's WaveNet ResidualBlock: one fused f32 MFMA launch per layer, the skip sum in place
+  wavenet   -- the diffusion denoiser's WaveNet ResidualBlock: one fused f32 MFMA launch per layer, the skip sum in place; two launches in its channel-split form for real-time sizes
   naive_v2  -- the reflow / diffusion-fast denoiser's NaiveV2DiffLayer: two fused f32 MFMA launches per layer, four in its channel-split form for real-time sizes
   loss      -- ddsp/loss.py SSSLoss / RSSLoss (the STFT of any size below 2049 as an in-kernel chirp-z transform, the loss and
                its gradient in the same kernels; torch.stft only above that)

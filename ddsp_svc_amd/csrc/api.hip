@@ -10,6 +10,7 @@
 #include "generator_tail.h"
 #include "conformer_conv.h"
 #include "wavenet_layer.h"
+#include "wavenet_split.h"
 #include "performer_attention.h"
 #include "naive_v2_layer.h"
 #include "naive_v2_split.h"
@@ -1559,6 +1560,27 @@ int ddsp_hip_wavenet_layer(const float* x, const float* cond, const float* d, fl
   if (packed_bytes < wavenet_layer_pack_bytes(C, H)) return DDSP_HIP_EWS;
   if (reinterpret_cast<uintptr_t>(packed) & 3) return DDSP_HIP_EINVAL;
   launch_wavenet_layer(x, cond, d, x_out, skip, static_cast<const float*>(packed), B, T, C, H, skip_mode, S(stream));
+  return finish();
+}
+
+int ddsp_hip_wavenet_layer_split_tile(int C, int H) { return wnet::shape_ok(C, H) ? wns::kT : 0; }
+
+size_t ddsp_hip_wavenet_layer_split_workspace_bytes(long B, long T, int C) {
+  if (B < 1 || T < 1 || !wnet::shape_ok(C, 256) || !wns::in_range(B, T)) return 0;
+  return wavenet_split_ws_bytes(B, T, C);
+}
+
+int ddsp_hip_wavenet_layer_split(const float* x, const float* cond, const float* d, float* x_out, float* skip, const void* packed,
+                                 size_t packed_bytes, void* ws, size_t ws_bytes, int B, long T, int C, int H, int skip_mode,
+                                 void* stream) {
+  if (B < 0 || T < 1 || (skip_mode != 0 && skip_mode != 1)) return DDSP_HIP_EINVAL;
+  if (!wnet::shape_ok(C, H) || T > (1L << 40) || !wns::in_range(B, T)) return DDSP_HIP_ESHAPE;
+  if (B == 0) return 0;
+  if (!x || !cond || !d || !x_out || !skip || !packed || !ws || x_out == x || skip == x || skip == x_out) return DDSP_HIP_EINVAL;
+  if (packed_bytes < wavenet_layer_pack_bytes(C, H) || ws_bytes < wavenet_split_ws_bytes(B, T, C)) return DDSP_HIP_EWS;
+  if ((reinterpret_cast<uintptr_t>(packed) & 3) || (reinterpret_cast<uintptr_t>(ws) & 3)) return DDSP_HIP_EINVAL;
+  launch_wavenet_split(x, cond, d, x_out, skip, static_cast<const float*>(packed), static_cast<float*>(ws), B, T, C, H, skip_mode,
+                       S(stream));
   return finish();
 }
 

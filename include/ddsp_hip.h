@@ -625,6 +625,24 @@ int ddsp_hip_wavenet_layer_pack(const float* wdil, const float* bdil, const floa
 int ddsp_hip_wavenet_layer(const float* x, const float* cond, const float* d, float* x_out, float* skip, const void* packed,
                            size_t packed_bytes, int B, long T, int C, int H, int skip_mode, void* stream);
 
+/* The same layer in its channel-split form, csrc/wavenet_split.h, for calls of a few hundred frames: a frame tile of 16, the
+ * channels split over workgroups and waves, two plain launches on the stream (the gate g = sigmoid(z[:C]) tanh(z[C:]) into the
+ * workspace, then the output GEMM with the tiled kernel's epilogue), every sum in the order of ddsp_hip_wavenet_layer, so the two
+ * give the same bits.  It reads the table of ddsp_hip_wavenet_layer_pack.  As above, these entry points came after version 165
+ * without a version step.
+ * ddsp_hip_wavenet_layer_split_tile: frames per workgroup (16); 0 for a (C, H) the kernels do not take.
+ * ddsp_hip_wavenet_layer_split_workspace_bytes: B T C floats (g [B, C, T]); 0 for C outside the shapes, B < 1, T < 1 and sizes
+ * past the cap below.
+ * ddsp_hip_wavenet_layer_split: the arguments, checks and error codes of ddsp_hip_wavenet_layer in the same order, and
+ * B ceil(T / 16) <= 4096 (DDSP_HIP_ESHAPE beyond, whatever the buffers are: the tiled form is for the rest), ws not null
+ * (DDSP_HIP_EINVAL) and of at least the bytes above (DDSP_HIP_EWS); every refusal comes before any launch.  54 KB of LDS per
+ * workgroup in the first launch at C = 512.  No allocation, no synchronisation. */
+int ddsp_hip_wavenet_layer_split_tile(int C, int H);
+size_t ddsp_hip_wavenet_layer_split_workspace_bytes(long B, long T, int C);
+int ddsp_hip_wavenet_layer_split(const float* x, const float* cond, const float* d, float* x_out, float* skip, const void* packed,
+                                 size_t packed_bytes, void* ws, size_t ws_bytes, int B, long T, int C, int H, int skip_mode,
+                                 void* stream);
+
 /* The performer (softmax-kernel linear) attention of PCmer (ddsp/pcmer.py:14-47, 218-232, 297-325), csrc/performer_attention.h.
  * As above, these entry points came after version 165 without a version step.  Per batch item and head, q, k, v [N, d], the
  * projection P [m, d], dn = d^-0.25, ratio = m^-0.5:

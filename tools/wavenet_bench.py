@@ -8,6 +8,11 @@ step by step.
                events around each call  -> profiles/wavenet_throughput.json
   latency      the same two at B x T = 1 x 100 (the streaming shape) and 1 x 203 (the GUI's 2.35 s window), call to result: a
                host clock around the call and a device synchronise  -> profiles/wavenet_latency.json
+  split        three sides -- the torch chain, the tiled form and the channel-split form (csrc/wavenet_split.h) -- at B x T =
+               1 x 100, 1 x 203, 1 x 862, 4 x 203 and 48 x 172, one layer and the 20-layer stack, alternated step by step, call
+               to result; split and tiled outputs must be torch.equal in every case  -> profiles/wavenet_split_latency.json;
+               ``split_below`` there is what wavenet.SPLIT_BELOW is filled from.  Not part of ``both``: it leaves the two files
+               above as they are.
 
 Each pair runs --steps alternated steps and is timed over the LAST --tail of them: the first ones run on a clock that is still
 settling (EXPERIMENTS.md 6.1), so a ramp of matrix products runs first.  The achieved fraction of the 155 TF f32 MFMA peak is
@@ -33,7 +38,8 @@ H = 256
 CHANNELS = (384, 512)
 LAYERS = 20
 PEAK_TFLOPS = 155.0                                    # measured f32 MFMA peak of one MI355X
-SHAPES = {"throughput": ((64, 862), (32, 862), (48, 172)), "latency": ((1, 100), (1, 203))}
+SHAPES = {"throughput": ((64, 862), (32, 862), (48, 172)), "latency": ((1, 100), (1, 203)),
+          "split": ((1, 100), (1, 203), (1, 862), (4, 203), (48, 172))}
 STEP_LIMIT_S = 240                                     # per child
 
 
@@ -94,6 +100,70 @@ def compare(hip, ref, steps, tail, events):
             "hip_ms_first_steps": float(np.median(th[:5])) * 1e3, "max_abs_diff_over_rms": diff}
 
 
+def compare3(sides, steps, tail):
+    """alternated: torch, tiled, split, torch, ...; call to result; the median and spread of each over the last ``tail`` steps.
+    ``sides``: name -> callable returning (x_out, skip)."""
+    out = {k: [t.clone() for t in fn()] for k, fn in sides.items()}
+    torch.cuda.synchronize()
+    assert all(torch.equal(a, b) for a, b in zip(out["split"], out["tiled"])), "the split and the tiled form differ"
+    r = {"split_equals_tiled": True,
+         "max_abs_diff_over_rms": max(float((a - b).abs().max() / b.pow(2).mean().sqrt()) for a, b in zip(out["split"], out["torch"]))}
+    del out
+    times = {k: [] for k in sides}
+    for _ in range(steps):
+        for k, fn in sides.items():
+            times[k].append(timed(fn, False))
+    for k, v in times.items():
+        m, lo, hi = [float(np.percentile(v[-tail:], p)) * 1e3 for p in (50, 10, 90)]
+        r[k + "_ms"], r[k + "_ms_p10_p90"] = m, [lo, hi]
+    r["fastest"] = min(sides, key=lambda k: r[k + "_ms"])
+    return r
+
+
+def run_split(C, steps, tail):
+    from ddsp_svc_amd import wavenet as WN
+    dev = torch.device("cuda:0")
+    layers = [make_layer(dev, C, 10 + i) for i in range(LAYERS)]
+    cases = []
+    ramp(dev)
+    with torch.no_grad():
+        for B, T in SHAPES["split"]:
+            gen = torch.Generator().manual_seed(B + T)
+            x, cond = torch.randn(B, C, T, generator=gen).to(dev), torch.randn(B, H, T, generator=gen).to(dev)
+            s = torch.randn(B, C, generator=gen).to(dev)
+            out, skip = torch.empty_like(x), torch.empty_like(x)
+            w0, (wp0, bp0) = layers[0]
+            layer = lambda form: lambda: WN.residual_layer(x, cond, torch.addmm(bp0, s, wp0.t()), w0, out=out, skip=skip, form=form)
+            stack = lambda form: lambda: WN.residual_stack(x, cond, s, layers, form=form)
+            todo = (("layer", 1, steps, {"torch": lambda: torch_layer(x, cond, s, layers[0]), "tiled": layer("tiled"),
+                                         "split": layer("split")}),
+                    ("stack20", LAYERS, max(steps // 4, 8), {"torch": lambda: torch_stack(x, cond, s, layers), "tiled": stack("tiled"),
+                                                             "split": stack("split")}))
+            for name, n, k, sides in todo:
+                r = compare3(sides, k, min(tail, k))
+                r.update(case=name, C=C, B=B, T=T, frames=B * T, steps=k, launches_tiled=n, launches_split=2 * n,
+                         tiles_split=B * -(-T // 16), workspace_bytes_split=B * T * C * 4)
+                cases.append(r)
+                print(json.dumps(r), flush=True)
+            del x, cond, out, skip
+            WN.release_workspace()
+            torch.cuda.empty_cache()
+    return {"tile": WN.tile(C, H), "tile_split": WN.split_tile(C, H), "device": torch.cuda.get_device_name(0),
+            "torch": torch.__version__, "cases": cases}
+
+
+def split_below(cases):
+    """C -> the smallest measured size at which the split form was not the fastest of the three (one past the largest measured
+    size if it was the fastest at all of them); no entry if it is not the fastest at the smallest size"""
+    table = {}
+    for C in sorted({c["C"] for c in cases}):
+        mine = sorted((c["frames"], c["fastest"]) for c in cases if c["case"] == "layer" and c["C"] == C)
+        if mine and mine[0][1] == "split":
+            lost = [n for n, side in mine if side != "split"]
+            table[str(C)] = lost[0] if lost else mine[-1][0] + 1
+    return table
+
+
 def flops(C, B, T, layers, tile):
     per_frame = 2.0 * 2 * C * (4 * C + H)
     return per_frame * B * T * layers, per_frame * B * (-(-T // tile) * tile) * layers
@@ -149,7 +219,7 @@ def run(mode, C, steps, tail):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=("latency", "throughput", "both"), default="both")
+    ap.add_argument("--mode", choices=("latency", "throughput", "both", "split"), default="both")
     ap.add_argument("--steps", type=int, default=60)
     ap.add_argument("--tail", type=int, default=20)
     ap.add_argument("--out-dir", default=os.path.join(ROOT, "profiles"))
@@ -160,7 +230,8 @@ def main():
     if args.child:
         mode, C, path = args.child[0], int(args.child[1]), args.child[2]
         with open(path, "w") as f:
-            json.dump(run(mode, C, args.steps, min(args.tail, args.steps)), f)
+            tail = min(args.tail, args.steps)
+            json.dump(run_split(C, args.steps, tail) if mode == "split" else run(mode, C, args.steps, tail), f)
         return
     os.makedirs(args.out_dir, exist_ok=True)
     for mode in (("throughput", "latency") if args.mode == "both" else (args.mode,)):
@@ -168,8 +239,9 @@ def main():
         doc = {"mode": mode, "C": list(CHANNELS), "H": H, "layers_of_the_stack": LAYERS, "steps": args.steps,
                "timed_over_last": args.tail, "peak_tflops": PEAK_TFLOPS,
                "timing": "device events" if events else "host clock + synchronise", "cases": []}
+        stem = "wavenet_split_latency" if mode == "split" else "wavenet_%s" % mode
         for C in CHANNELS:
-            part = os.path.join(args.out_dir, ".wavenet_%s_%d.part" % (mode, C))
+            part = os.path.join(args.out_dir, ".%s_%d.part" % (stem, C))
             cmd = ["timeout", "-k", "10", str(STEP_LIMIT_S), sys.executable, os.path.abspath(__file__), "--steps", str(args.steps),
                    "--tail", str(args.tail), "--child", mode, str(C), part]
             code = subprocess.call(cmd)
@@ -180,9 +252,12 @@ def main():
             os.remove(part)
             doc["cases"] += got.pop("cases")
             doc.update(got)
-        doc["torch_faster_frames"] = {str(C): sorted({c["frames"] for c in doc["cases"] if c["C"] == C and c["case"] == "layer"
-                                                      and c["torch_over_hip"] < 1.0}) for C in CHANNELS}
-        path = os.path.join(args.out_dir, "wavenet_%s.json" % mode)
+        if mode == "split":
+            doc["split_below"] = split_below(doc["cases"])
+        else:
+            doc["torch_faster_frames"] = {str(C): sorted({c["frames"] for c in doc["cases"] if c["C"] == C and c["case"] == "layer"
+                                                          and c["torch_over_hip"] < 1.0}) for C in CHANNELS}
+        path = os.path.join(args.out_dir, "%s.json" % stem)
         with open(path, "w") as f:
             f.write(json.dumps(doc, indent=1) + "\n")
         print("wrote", path, flush=True)
