@@ -1,5 +1,7 @@
-"""What the reference-module hooks (``nsf_generator``, ``conformer``, ``mel``) share: the cache of packed weight tables, the
-predicates their eligibility checks are made of and the rule of the per-stream workspaces (``attention``, ``naive_v2``).
+"""What the reference-module hooks (``nsf_generator``, ``conformer``, ``attention``, ``wavenet``, ``naive_v2``) share: the cache of
+packed weight tables and the staging of a host table, the per-stream workspaces, the predicates their eligibility checks are made
+of, and what the two denoiser layers (``wavenet``, ``naive_v2``) have in common: the stacked step projections, the rule that
+routes a size to the split form, the tiled form or torch.  ``mel`` uses ``needs_grad``.
 
 The cache rule: a table is found again by the device, the kind of kernel, the shape integers and the ``data_ptr`` of every
 parameter tensor; it is a hit only while every tensor's ``_version`` is the one it was packed at (an in-place write packs
@@ -40,12 +42,58 @@ def clear_packed():
         _PACKED.clear()
 
 
+def pack_host(nbytes, refusal, tensors, entry, dims):
+    """the host table that a caller's ``pack`` returns: ``nbytes`` is what its C ``*_pack_bytes`` entry answered (0: ValueError
+    with ``refusal``), ``tensors`` are staged as contiguous CPU float32, and ``entry``, its C ``*_pack``, fills the table from the
+    staged pointers, ``dims`` (with whatever further pointers the entry takes in front), the table and its size"""
+    if nbytes == 0:
+        raise ValueError(refusal)
+    with torch.no_grad():
+        staged = [t.detach().to("cpu", torch.float32).contiguous() for t in tensors]
+    host = torch.empty(nbytes // 4, dtype=torch.float32)
+    _ffi.check(entry(*[t.data_ptr() for t in staged], *dims, host.data_ptr(), nbytes))
+    return host
+
+
+_STACKED = {}                                          # data_ptrs of the projections -> (versions, W [n C, C], b [n C], kept)
+_STACKED_MAX = 32                                      # for both denoisers: as many as the 16 each of them kept on its own
+
+
+def stacked_projection(projs):
+    """``(W [n C, C], b [n C])``: the layers' ``(weight [C, C] or [C, C, 1], bias [C])`` step projections stacked, cached by the
+    rule of ``packed_table`` (found again by every tensor's ``data_ptr``, a hit while every ``_version`` is unchanged, the entry
+    keeps the tensors alive, ``_STACKED_MAX`` entries dropped oldest first, under the same lock)"""
+    flat = [t for p in projs for t in p]
+    key = tuple(t.data_ptr() for t in flat)
+    versions = tuple(t._version for t in flat)
+    with _LOCK:
+        hit = _STACKED.get(key)
+        if hit is not None and hit[0] == versions:
+            return hit[1], hit[2]
+        with torch.no_grad():
+            W = torch.cat([p[0].detach().reshape(p[0].shape[0], -1) for p in projs], 0).contiguous()
+            b = torch.cat([p[1].detach() for p in projs], 0).contiguous()
+        while len(_STACKED) >= _STACKED_MAX:
+            _STACKED.pop(next(iter(_STACKED)))
+        _STACKED[key] = (versions, W, b, flat)
+    return W, b
+
+
+def step_biases(s, projs):
+    """``d [n, B, C]``: the step embedding ``s [B, C]`` through all n layers' projections in ONE matmul"""
+    W, b = stacked_projection(projs)
+    return torch.addmm(b, s, W.t()).view(s.shape[0], len(projs), W.shape[1]).transpose(0, 1).contiguous()
+
+
 _WS_LOCK = threading.Lock()
 
 
 def stream_workspace(cache, floats, x, keep):
     """the float32 buffer of at least ``floats`` elements that ``cache`` (a module's own ``OrderedDict``) holds for ``x``'s device
-    and the caller's current stream there: never shared between streams, grown on demand, the ``keep`` most recently used kept.
+    and the caller's current stream there: never shared between streams (the launches of one call write and read it on that
+    stream), grown on demand, the ``keep`` most recently used kept.  A buffer is allocated while its stream is the current one,
+    so the caching allocator hands its memory on only to later work of that same stream: a buffer that growth, the bound or
+    ``drop_workspaces`` drops while launches still use it is reused behind them, never beside them.
     During a graph capture the cache is neither read nor grown: the buffer then comes from the graph's pool and belongs to the
     graph, which holds no address that a later growth or ``drop_workspaces`` frees."""
     if x.is_cuda and torch.cuda.is_current_stream_capturing():
@@ -93,6 +141,39 @@ def plain(module):
             and not module._forward_hooks and module.weight.dtype == torch.float32)
 
 
+def plain_with_bias(module):
+    """``plain`` and a bias that is a plain float32 parameter too"""
+    return plain(module) and isinstance(module._parameters.get("bias"), torch.Tensor) and module.bias.dtype == torch.float32
+
+
+def pointwise(c, cin, cout):
+    """an unpadded ``Conv1d(cin, cout, 1)``, ``plain_with_bias``"""
+    return (isinstance(c, torch.nn.Conv1d) and plain_with_bias(c) and c.in_channels == cin and c.out_channels == cout
+            and c.kernel_size == (1,) and c.stride == (1,) and c.dilation == (1,) and c.groups == 1 and pad_of(c) == (0,))
+
+
 def torch_faster(table, key, size):
     """``table`` (a ``*_TORCH_FASTER``) lists ``key`` with a bound above ``size``, or with None: the torch chain at every size"""
     return key in table and (table[key] is None or size < table[key])
+
+
+# ---- the two forms of a denoiser layer (wavenet, naive_v2) --------------------------------------------------------------------
+
+SPLIT_TILE = 16                                        # frames per workgroup of a split form
+SPLIT_MAX_TILES = 4096                                 # a split form takes B ceil(n / 16) up to here
+FORMS = ("tiled", "split")
+
+
+def split_in_range(B, n):
+    """a split form takes ``B ceil(n / SPLIT_TILE)`` tiles up to ``SPLIT_MAX_TILES``"""
+    return B * -(-n // SPLIT_TILE) <= SPLIT_MAX_TILES
+
+
+def choose_form(split_below, faster, key, B, n):
+    """where a hook sends a layer call of ``B x n`` frames: ``"split"`` within the split form's range below the measured
+    ``split_below[key]``, else ``"tiled"`` unless ``faster`` (a ``*_TORCH_FASTER``) gives the size to torch, else None (the torch
+    chain).  The two forms give the same bits, so the choice never shows in a result."""
+    if key in split_below and split_in_range(B, n) and B * n < split_below[key]:
+        return "split"
+    return None if torch_faster(faster, key, B * n) else "tiled"
+

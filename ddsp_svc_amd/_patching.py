@@ -1,5 +1,8 @@
 """Park, swap, undo: how every ``patch_reference_*`` puts a dispatcher in the place of one of the reference's own names.  The
-original is parked next to it as ``_reference_<name>``, once; the swap is the caller's; the undo binds the original back."""
+original is parked next to it as ``_reference_<name>``, once; the swap is the caller's; the undo binds the original back.
+``patch_forwards`` / ``unpatch_forwards`` are that rule for the ``forward`` of a list of classes in a list of modules, and
+``run_reference`` is how a dispatcher reaches the parked original again."""
+import importlib
 import sys
 
 
@@ -16,6 +19,48 @@ def unpark(owner, name):
     if "_reference_" + name in vars(owner):
         setattr(owner, name, getattr(owner, "_reference_" + name))
         delattr(owner, "_reference_" + name)
+
+
+def patch_forwards(modules, classes):
+    """Bind ``fwd`` as ``cls.forward`` for every ``(class name, fwd)`` of ``classes`` that each of ``modules`` (names to import, or
+    module objects) holds, the original parked.  A name that does not import is skipped (a reference module whose own imports
+    are missing here: nothing to patch), and so is a class that is not there.  Idempotent: only a ``forward`` that is still the
+    parked original is replaced.  Returns the module objects it went through."""
+    done = []
+    for mod in modules:
+        if isinstance(mod, str):
+            try:
+                mod = importlib.import_module(mod)
+            except Exception:                            # noqa: BLE001
+                continue
+        for cls_name, fwd in classes:
+            cls = getattr(mod, cls_name, None)
+            if cls is not None and cls.forward is park(cls, "forward"):
+                cls.forward = fwd
+        done.append(mod)
+    return done
+
+
+def unpatch_forwards(modules, class_names):
+    """Undo ``patch_forwards``: ``unpark`` the ``forward`` of every class of ``class_names`` that each of ``modules`` holds; a name
+    is looked up in ``sys.modules`` (never imported), a module object is taken as it is."""
+    for mod in modules:
+        mod = sys.modules.get(mod) if isinstance(mod, str) else mod
+        for cls_name in class_names:
+            if hasattr(mod, cls_name):
+                unpark(getattr(mod, cls_name), "forward")
+
+
+def run_reference(obj, fallback, *args, **kw):
+    """What a dispatcher hands a call that the kernels do not take: the parked ``_reference_forward`` of ``obj``'s type, called
+    as the method it was; where nothing is parked (a stand-in class of the tests and tools) ``fallback(*args, **kw)``;
+    AttributeError without either."""
+    ref = getattr(type(obj), "_reference_forward", None)
+    if ref is not None:
+        return ref(obj, *args, **kw)
+    if fallback is None:
+        raise AttributeError("%s has no parked _reference_forward and its dispatcher names no fallback" % type(obj).__name__)
+    return fallback(*args, **kw)
 
 
 def rebind_everywhere(mapping, skip=()):

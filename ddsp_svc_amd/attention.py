@@ -27,8 +27,9 @@ import torch
 import torch.nn.functional as F
 
 from . import _ffi
-from ._modules import drop_workspaces, needs_grad, on_device, packed_table, plain, stream_workspace, torch_faster
-from ._patching import park, unpark
+from ._modules import (drop_workspaces, needs_grad, on_device, pack_host, packed_table, plain_with_bias, stream_workspace,
+                       torch_faster)
+from ._patching import patch_forwards, run_reference, unpatch_forwards
 
 DIM_HEAD = 64
 FEATURES = 266
@@ -67,14 +68,9 @@ def release_workspace():
 
 def _pack(dims, tensors):
     """the host table of a projection matrix, for ``packed_table``"""
-    (d, m), lib = dims, _ffi.lib()
-    nbytes = int(lib.ddsp_hip_performer_pack_bytes(d, m))
-    if nbytes == 0:
-        raise ValueError("fast_attention: (dim_head, features) = (%d, %d) is outside the kernel's range" % (d, m))
-    with torch.no_grad():
-        proj = tensors[0].detach().to("cpu", torch.float32).contiguous()
-    host = torch.empty(nbytes // 4, dtype=torch.float32)
-    _ffi.check(lib.ddsp_hip_performer_pack(proj.data_ptr(), d, m, host.data_ptr(), nbytes))
+    lib = _ffi.lib()
+    refusal = "fast_attention: (dim_head, features) = (%d, %d) is outside the kernel's range" % dims
+    host = pack_host(int(lib.ddsp_hip_performer_pack_bytes(*dims)), refusal, tensors[:1], lib.ddsp_hip_performer_pack, dims)
     PACKS["count"] += 1
     return host
 
@@ -203,8 +199,7 @@ def fast_eligible(module, q, k, v):
 
 
 def _linear(m, cout=None):
-    return (isinstance(m, torch.nn.Linear) and plain(m) and isinstance(m._parameters.get("bias"), torch.Tensor)
-            and m.bias.dtype == torch.float32 and (cout is None or m.out_features == cout))
+    return isinstance(m, torch.nn.Linear) and plain_with_bias(m) and (cout is None or m.out_features == cout)
 
 
 def self_eligible(module, x, context=None, mask=None, context_mask=None):
@@ -237,7 +232,7 @@ def self_eligible(module, x, context=None, mask=None, context_mask=None):
 
 def _reference(module, *args, **kw):
     CALLS["reference"] += 1
-    return type(module)._reference_forward(module, *args, **kw)
+    return run_reference(module, None, *args, **kw)
 
 
 def fast_forward(module, q, k, v):
@@ -263,33 +258,12 @@ _CLASSES = (("FastAttention", lambda self, q, k, v: fast_forward(self, q, k, v))
 
 
 def patch_reference_attention(modules=None):
-    """Route ``FastAttention.forward`` and ``SelfAttention.forward`` of ``ddsp.pcmer`` (where it imports; or of the module
-    objects given) through the dispatchers above.  Idempotent; returns the list of modules patched.
-    ``vocoder.patch_reference()`` does not call it: the hook is opt-in."""
-    import importlib
-    done = []
-    for name in (_REFERENCE_MODULES if modules is None else modules):
-        if isinstance(name, str):
-            try:
-                mod = importlib.import_module(name)
-            except Exception:                          # not importable here (ddsp.pcmer needs local_attention): nothing to patch
-                continue
-        else:
-            mod = name
-        for cls_name, fwd in _CLASSES:
-            cls = getattr(mod, cls_name, None)
-            if cls is not None and cls.forward is park(cls, "forward"):
-                cls.forward = fwd
-        done.append(mod)
-    return done
+    """Route ``FastAttention.forward`` and ``SelfAttention.forward`` of ``ddsp.pcmer`` (where it imports: it needs
+    local_attention; or of the module names or objects given) through the dispatchers above.  Idempotent; returns the list of
+    modules patched.  ``vocoder.patch_reference()`` does not call it: the hook is opt-in."""
+    return patch_forwards(_REFERENCE_MODULES if modules is None else modules, _CLASSES)
 
 
 def unpatch_reference_attention(modules=None):
     """Undo ``patch_reference_attention()``."""
-    for name in (_REFERENCE_MODULES if modules is None else modules):
-        mod = sys.modules.get(name) if isinstance(name, str) else name
-        if mod is None:
-            continue
-        for cls_name, _ in _CLASSES:
-            if hasattr(mod, cls_name):
-                unpark(getattr(mod, cls_name), "forward")
+    unpatch_forwards(_REFERENCE_MODULES if modules is None else modules, [name for name, _ in _CLASSES])

@@ -19,8 +19,8 @@ B L below which the same-GPU torch chain was measured faster (tools/conformer_be
 import torch
 
 from . import _ffi
-from ._modules import needs_grad, on_device, packed_table, pad_of, plain, torch_faster
-from ._patching import park, unpark
+from ._modules import needs_grad, on_device, pack_host, packed_table, pad_of, plain_with_bias, pointwise, torch_faster
+from ._patching import patch_forwards, run_reference, unpatch_forwards
 
 DIMS = (256,)
 TAPS = 31
@@ -41,14 +41,9 @@ def tile(D):
 def _pack(dims, flat):
     """the host table of ``(w1, b1, wd, bd, w2, b2)`` and, with ``dims = (D, True)``, ``(gamma, beta)``, for ``packed_table``"""
     (D, normed), lib = dims, _ffi.lib()
-    nbytes = int(lib.ddsp_hip_conformer_conv_pack_bytes(D, int(normed)))
-    if nbytes == 0:
-        raise ValueError("conv_module: D = %d is outside the kernel's range" % D)
-    with torch.no_grad():
-        staged = [t.detach().to("cpu", torch.float32).contiguous() for t in flat]
-    host = torch.empty(nbytes // 4, dtype=torch.float32)
-    ptrs = [t.data_ptr() for t in staged] + ([] if normed else [None, None])
-    _ffi.check(lib.ddsp_hip_conformer_conv_pack(*ptrs, D, host.data_ptr(), nbytes))
+    refusal = "conv_module: D = %d is outside the kernel's range" % D
+    host = pack_host(int(lib.ddsp_hip_conformer_conv_pack_bytes(D, int(normed))), refusal, flat, lib.ddsp_hip_conformer_conv_pack,
+                     (D,) if normed else (None, None, D))                    # no LayerNorm: no gamma and beta to pack
     PACKS["count"] += 1
     return host
 
@@ -115,17 +110,6 @@ def encoder(x, layers, out=None):
 
 # ---- the reference's modules --------------------------------------------------------------------------------------------------
 
-def _plain(c):
-    """``_modules.plain`` and a bias that is a plain float32 parameter too"""
-    return plain(c) and isinstance(c._parameters.get("bias"), torch.Tensor) and c.bias.dtype == torch.float32
-
-
-def _pointwise(c, cin, cout):
-    return (isinstance(c, torch.nn.Conv1d) and _plain(c) and c.in_channels == cin and c.out_channels == cout
-            and c.kernel_size == (1,) and c.stride == (1,) and c.dilation == (1,) and c.groups == 1
-            and pad_of(c) == (0,))
-
-
 def _depthwise(m, C):
     """the depthwise Conv1d of either form: ``Conv1d(C, C, 31, padding=15, groups=C)``, or a wrapper that pads by (15, 15) and
     then runs an unpadded grouped ``conv``"""
@@ -141,8 +125,8 @@ def _depthwise(m, C):
         if not isinstance(m, torch.nn.Module) or m._forward_pre_hooks or m._forward_hooks:
             return None
         pad = tuple(pad)
-    if (pad != (TAPS // 2, TAPS // 2) or not _plain(conv) or conv.in_channels != C or conv.out_channels != C or conv.groups != C
-            or conv.kernel_size != (TAPS,) or conv.stride != (1,) or conv.dilation != (1,)):
+    if (pad != (TAPS // 2, TAPS // 2) or not plain_with_bias(conv) or conv.in_channels != C or conv.out_channels != C
+            or conv.groups != C or conv.kernel_size != (TAPS,) or conv.stride != (1,) or conv.dilation != (1,)):
         return None
     return conv
 
@@ -179,7 +163,7 @@ def _conv_spec(module):
         return None
     if any(m._forward_pre_hooks or m._forward_hooks for m in (t1, glu, act, t2, drop)):
         return None
-    if not _pointwise(c1, D, 4 * D) or not _pointwise(c2, 2 * D, D):
+    if not pointwise(c1, D, 4 * D) or not pointwise(c2, 2 * D, D):
         return None
     conv = _depthwise(dw, 2 * D)
     if conv is None:
@@ -210,10 +194,7 @@ def conv_eligible(module, x):
 
 def _reference_conv_forward(module, x):
     CALLS["reference"] += 1
-    ref = getattr(type(module), "_reference_forward", None)
-    if ref is not None:
-        return ref(module, x)
-    return module.net(x)
+    return run_reference(module, getattr(module, "net", None), x)
 
 
 def conv_forward(module, x):
@@ -240,40 +221,18 @@ def layer_forward(layer, x, mask=None):
 _REFERENCE_MODULES = ("diffusion.model_conformer_naive", "reflow.model_conformer_naive", "ddsp.pcmer")
 
 
-def _conv_module_forward(self, x):
-    return conv_forward(self, x)
-
-
-def _encoder_layer_forward(self, x, mask=None):
-    return layer_forward(self, x, mask)
+_CLASSES = (("ConformerConvModule", lambda self, x: conv_forward(self, x)),
+            ("CFNEncoderLayer", lambda self, x, mask=None: layer_forward(self, x, mask)))
 
 
 def patch_reference_conformer():
     """Route ``ConformerConvModule.forward`` and ``CFNEncoderLayer.forward`` of whichever of the reference's modules import
-    (``diffusion.model_conformer_naive``, ``reflow.model_conformer_naive``, ``ddsp.pcmer``) through the dispatchers above.
-    Idempotent; returns the list of modules patched.  ``vocoder.patch_reference()`` does not call it: the hook is opt-in."""
-    import importlib
-    done = []
-    for name in _REFERENCE_MODULES:
-        try:
-            mod = importlib.import_module(name)
-        except Exception:                              # not importable here (ddsp.pcmer needs local_attention): nothing to patch
-            continue
-        for cls_name, fwd in (("ConformerConvModule", _conv_module_forward), ("CFNEncoderLayer", _encoder_layer_forward)):
-            cls = getattr(mod, cls_name, None)
-            if cls is not None and cls.forward is park(cls, "forward"):
-                cls.forward = fwd
-        done.append(mod)
-    return done
+    (``diffusion.model_conformer_naive``, ``reflow.model_conformer_naive``, ``ddsp.pcmer``, which needs local_attention) through
+    the dispatchers above.  Idempotent; returns the list of modules patched.  ``vocoder.patch_reference()`` does not call it:
+    the hook is opt-in."""
+    return patch_forwards(_REFERENCE_MODULES, _CLASSES)
 
 
 def unpatch_reference_conformer():
     """Undo ``patch_reference_conformer()``."""
-    import sys
-    for name in _REFERENCE_MODULES:
-        mod = sys.modules.get(name)
-        if mod is None:
-            continue
-        for cls_name in ("ConformerConvModule", "CFNEncoderLayer"):
-            if hasattr(mod, cls_name):
-                unpark(getattr(mod, cls_name), "forward")
+    unpatch_forwards(_REFERENCE_MODULES, [name for name, _ in _CLASSES])

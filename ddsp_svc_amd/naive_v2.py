@@ -26,15 +26,15 @@ a frame tile of 16 and the channels split over workgroups, four launches, for ca
 ``choose_form`` is the one place where the hook decides between the split form, the tiled form and torch.
 """
 import collections
-import threading
 
 import torch
 import torch.nn.functional as F
 
-from . import _ffi
+from . import _ffi, _modules
 from . import conformer as _conformer
-from ._modules import drop_workspaces, needs_grad, on_device, packed_table, pad_of, plain, stream_workspace, torch_faster
-from ._patching import park, unpark
+from ._modules import (FORMS, SPLIT_MAX_TILES, drop_workspaces, needs_grad, on_device, pack_host, packed_table, pointwise,
+                       step_biases, stream_workspace)
+from ._patching import patch_forwards, run_reference, unpatch_forwards
 
 SHAPES = ((512, 128),)
 TAPS = 31
@@ -50,17 +50,12 @@ LAYER_TORCH_FASTER = {512: 27584}
 # was the fastest at all five measured sizes -- 1 x 100, 1 x 203, 4 x 203, 1 x 862 (x1.88, x1.67, x1.32, x1.51 over torch) and, by
 # 3 %, 48 x 172 = 8 256 frames --, so the bound is one past the largest of them: nothing above it was measured.
 SPLIT_BELOW = {512: 8257}
-SPLIT_MAX_TILES = 4096                                 # the split form takes B ceil(L / 16) up to here
-FORMS = ("tiled", "split")
 # dispatch counters (tests and tools read them): layer calls ("hip": on the kernels in either form, "split": those of them that
 # took the split form); separate from conformer.CALLS and wavenet.CALLS
 CALLS = {"hip": 0, "reference": 0, "split": 0}
 PACKS = {"count": 0}                                   # weight tables built (a cache hit does not count)
-_LOCK = threading.Lock()                               # guards _STACKED
 _WS = collections.OrderedDict()                        # (device, stream) -> the buffer the GLU's output passes through
 _WS_MAX = 16
-_STACKED = {}                                          # data_ptrs of the projection weights -> (versions, W [n D, D], b [n D], kept)
-_STACKED_MAX = 16
 
 
 def tile(D, Hc):
@@ -75,17 +70,15 @@ def split_tile(D, Hc):
 
 
 def split_in_range(B, L):
-    """the split form takes ``B ceil(L / 16)`` tiles up to ``SPLIT_MAX_TILES``"""
-    return B * -(-L // 16) <= SPLIT_MAX_TILES
+    """the split form takes ``B ceil(L / 16)`` tiles up to ``SPLIT_MAX_TILES`` (``_modules.split_in_range``)"""
+    return _modules.split_in_range(B, L)
 
 
 def choose_form(D, B, L):
     """where the hook sends a layer call of ``B x L`` frames: ``"split"`` within the split form's range below the measured
-    ``SPLIT_BELOW[D]``, else ``"tiled"`` unless ``LAYER_TORCH_FASTER`` gives the size to torch, else None (the torch chain).
-    The two forms give the same bits, so the choice never shows in a result."""
-    if D in SPLIT_BELOW and split_in_range(B, L) and B * L < SPLIT_BELOW[D]:
-        return "split"
-    return None if torch_faster(LAYER_TORCH_FASTER, D, B * L) else "tiled"
+    ``SPLIT_BELOW[D]``, else ``"tiled"`` unless ``LAYER_TORCH_FASTER`` gives the size to torch, else None (the torch chain):
+    ``_modules.choose_form`` on this module's two tables as they are now"""
+    return _modules.choose_form(SPLIT_BELOW, LAYER_TORCH_FASTER, D, B, L)
 
 
 def _workspace(B, L, D, x, form="tiled"):
@@ -103,14 +96,9 @@ def release_workspace():
 
 def _pack(dims, flat):
     """the host table of ``(wc, bc, w1, b1, wd, bd, w2, b2)``, for ``packed_table``"""
-    (D, Hc), lib = dims, _ffi.lib()
-    nbytes = int(lib.ddsp_hip_naive_v2_layer_pack_bytes(D, Hc))
-    if nbytes == 0:
-        raise ValueError("diff_layer: (D, Hc) = (%d, %d) is outside the kernels' range" % (D, Hc))
-    with torch.no_grad():
-        staged = [t.detach().to("cpu", torch.float32).contiguous() for t in flat]
-    host = torch.empty(nbytes // 4, dtype=torch.float32)
-    _ffi.check(lib.ddsp_hip_naive_v2_layer_pack(*[t.data_ptr() for t in staged], D, Hc, host.data_ptr(), nbytes))
+    lib = _ffi.lib()
+    refusal = "diff_layer: (D, Hc) = (%d, %d) is outside the kernels' range" % dims
+    host = pack_host(int(lib.ddsp_hip_naive_v2_layer_pack_bytes(*dims)), refusal, flat, lib.ddsp_hip_naive_v2_layer_pack, dims)
     PACKS["count"] += 1
     return host
 
@@ -148,7 +136,7 @@ def diff_layer(x, cond, d, weights, out=None, ws=None, form="tiled"):
         raise ValueError("diff_layer: L must be positive")
     if form not in FORMS:
         raise ValueError("diff_layer: form must be 'tiled' or 'split'")
-    if form == "split" and not split_in_range(B, L):
+    if form == "split" and not _modules.split_in_range(B, L):
         raise ValueError("diff_layer: the split form takes B ceil(L / 16) <= %d tiles" % SPLIT_MAX_TILES)
     if out is x or out is cond:
         raise ValueError("diff_layer: out must be neither x nor cond")
@@ -173,25 +161,6 @@ def diff_layer(x, cond, d, weights, out=None, ws=None, form="tiled"):
     return y
 
 
-def _stacked_projection(projs):
-    """``(W [n D, D], b [n D])``: the layers' ``(weight [D, D, 1], bias [D])`` step projections stacked, cached by the rule of
-    ``_modules.packed_table`` (found again by every tensor's ``data_ptr``, a hit while every ``_version`` is unchanged)"""
-    flat = [t for p in projs for t in p]
-    key = tuple(t.data_ptr() for t in flat)
-    versions = tuple(t._version for t in flat)
-    with _LOCK:
-        hit = _STACKED.get(key)
-        if hit is not None and hit[0] == versions:
-            return hit[1], hit[2]
-        with torch.no_grad():
-            W = torch.cat([p[0].detach().reshape(p[0].shape[0], -1) for p in projs], 0).contiguous()
-            b = torch.cat([p[1].detach() for p in projs], 0).contiguous()
-        while len(_STACKED) >= _STACKED_MAX:
-            _STACKED.pop(next(iter(_STACKED)))
-        _STACKED[key] = (versions, W, b, flat)
-    return W, b
-
-
 def diff_stack(x, cond, s, layers, form="tiled"):
     """The layers of a denoiser: ``x [B, L, D]``, ``cond [B, L, Hc]``, ``s [B, D]`` (the step embedding), ``layers`` a list of
     ``(weights, (wp [D, D, 1], bp [D]))``.  The step projections of all layers are ONE matmul; then one launch pair per layer, x
@@ -205,11 +174,10 @@ def diff_stack(x, cond, s, layers, form="tiled"):
     n = len(layers)
     if tuple(s.shape) != (B, D) or any(tuple(p[0].shape) != (D, D, 1) or tuple(p[1].shape) != (D,) for _, p in layers):
         raise ValueError("diff_stack: s must be [B, D] and every step projection ([D, D, 1], [D])")
-    if form not in FORMS or (form == "split" and not split_in_range(B, L)):
+    if form not in FORMS or (form == "split" and not _modules.split_in_range(B, L)):
         raise ValueError("diff_stack: form must be 'tiled' or 'split', the latter with B ceil(L / 16) <= %d" % SPLIT_MAX_TILES)
     _ffi.check_device(x, cond, s)
-    W, b = _stacked_projection([p for _, p in layers])
-    d = torch.addmm(b, s, W.t()).view(B, n, D).transpose(0, 1).contiguous()              # [n, B, D]
+    d = step_biases(s, [p for _, p in layers])                                            # [n, B, D]
     cond = cond.contiguous()
     bufs = (torch.empty_like(x, memory_format=torch.contiguous_format),
             torch.empty_like(x, memory_format=torch.contiguous_format) if n > 1 else None)
@@ -223,12 +191,6 @@ def diff_stack(x, cond, s, layers, form="tiled"):
 
 
 # ---- the reference's modules --------------------------------------------------------------------------------------------------
-
-def _pointwise(c, cin, cout):
-    return (isinstance(c, torch.nn.Conv1d) and plain(c) and isinstance(c._parameters.get("bias"), torch.Tensor)
-            and c.bias.dtype == torch.float32 and c.in_channels == cin and c.out_channels == cout and c.kernel_size == (1,)
-            and c.stride == (1,) and c.dilation == (1,) and c.groups == 1 and pad_of(c) == (0,))
-
 
 def _layer_spec(layer):
     """``(weights, (wp, bp))`` of a module with the layer's submodules in the kernels' form, or None"""
@@ -247,7 +209,7 @@ def _layer_spec(layer):
     if norm is not None or (drop.p != 0 and drop.training):
         return None
     D, Hc = cw[0].shape[1], cp.in_channels
-    if not _pointwise(sp, D, D) or not _pointwise(cp, Hc, D):
+    if not pointwise(sp, D, D) or not pointwise(cp, Hc, D):
         return None
     return (cp.weight, cp.bias) + tuple(cw), (sp.weight, sp.bias)
 
@@ -277,10 +239,7 @@ def layer_eligible(layer, x, cond, step):
 
 def _reference_layer_forward(layer, x, condition, diffusion_step):
     CALLS["reference"] += 1
-    ref = getattr(type(layer), "_reference_forward", None)
-    if ref is not None:
-        return ref(layer, x, condition, diffusion_step)
-    return layer.reference_forward(x, condition, diffusion_step)
+    return run_reference(layer, getattr(layer, "reference_forward", None), x, condition, diffusion_step)
 
 
 def layer_forward(layer, x, condition=None, diffusion_step=None):
@@ -295,13 +254,6 @@ def layer_forward(layer, x, condition=None, diffusion_step=None):
     d = torch.addmm(bp, diffusion_step[:, :, 0], wp[:, :, 0].t())
     form = choose_form(x.shape[1], x.shape[0], x.shape[2])
     return diff_layer(x.transpose(1, 2), condition.transpose(1, 2), d, weights, form=form).transpose(1, 2)
-
-
-def _reference_net_forward(net, spec, diffusion_step, cond):
-    ref = getattr(type(net), "_reference_forward", None)
-    if ref is not None:
-        return ref(net, spec, diffusion_step, cond)
-    return net.reference_forward(spec, diffusion_step, cond)
 
 
 def _stack_candidate(net, spec, cond):
@@ -336,21 +288,15 @@ def net_forward(net, spec, diffusion_step, cond):
             y = diff_stack(x.transpose(1, 2), condition.transpose(1, 2), step.select(2, 0), specs, form)
             out = net.output_projection(y.transpose(1, 2))
             return out.unsqueeze(1) if spec.dim() == 4 else out
-    return _reference_net_forward(net, spec, diffusion_step, cond)
+    return run_reference(net, getattr(net, "reference_forward", None), spec, diffusion_step, cond)
 
 
 _REFERENCE_MODULES = ("diffusion.naive_v2_diff", "reflow.naive_v2_diff")
 
 
-def _layer_forward(self, x, condition=None, diffusion_step=None):
-    return layer_forward(self, x, condition, diffusion_step)
-
-
-def _net_forward(self, spec, diffusion_step, cond):
-    return net_forward(self, spec, diffusion_step, cond)
-
-
-_CLASSES = (("NaiveV2DiffLayer", _layer_forward), ("NaiveV2Diff", _net_forward))
+_CLASSES = (("NaiveV2DiffLayer", lambda self, x, condition=None, diffusion_step=None:
+             layer_forward(self, x, condition, diffusion_step)),
+            ("NaiveV2Diff", lambda self, spec, diffusion_step, cond: net_forward(self, spec, diffusion_step, cond)))
 
 
 def patch_reference_naive_v2():
@@ -358,28 +304,9 @@ def patch_reference_naive_v2():
     ``reflow.naive_v2_diff`` import through the dispatchers above.  Idempotent; returns the list of modules patched.
     ``vocoder.patch_reference()`` does not call it, and it leaves ``patch_reference_conformer`` alone: the hook is opt-in, and a
     layer that runs on the kernels never reaches its inner conv module."""
-    import importlib
-    done = []
-    for name in _REFERENCE_MODULES:
-        try:
-            mod = importlib.import_module(name)
-        except Exception:                              # not importable here: nothing to patch
-            continue
-        for cls_name, fwd in _CLASSES:
-            cls = getattr(mod, cls_name, None)
-            if cls is not None and cls.forward is park(cls, "forward"):
-                cls.forward = fwd
-        done.append(mod)
-    return done
+    return patch_forwards(_REFERENCE_MODULES, _CLASSES)
 
 
 def unpatch_reference_naive_v2():
     """Undo ``patch_reference_naive_v2()``."""
-    import sys
-    for name in _REFERENCE_MODULES:
-        mod = sys.modules.get(name)
-        if mod is None:
-            continue
-        for cls_name, _ in _CLASSES:
-            if hasattr(mod, cls_name):
-                unpark(getattr(mod, cls_name), "forward")
+    unpatch_forwards(_REFERENCE_MODULES, [name for name, _ in _CLASSES])

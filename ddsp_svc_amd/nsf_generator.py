@@ -27,14 +27,14 @@ and 256 -> 128 seams, weight-normed modules and calls that need a gradient run t
 """
 import collections
 import ctypes
-import threading
 
 import torch
 import torch.nn.functional as F
 
 from . import _ffi
-from ._modules import clear_packed, needs_grad, on_device, packed_table, pad_of, plain, torch_faster  # noqa: F401
-from ._patching import park, unpark
+from ._modules import (clear_packed, drop_workspaces, needs_grad, on_device, packed_table, pad_of, plain,  # noqa: F401
+                       stream_workspace, torch_faster)
+from ._patching import park, run_reference, unpark
 
 CHANNELS = (16, 32, 64)
 KERNEL_SIZES = (3, 7, 11)
@@ -49,9 +49,7 @@ HEAD_TAPS = 7
 SEAM_TORCH_FASTER = {}
 HEAD_TORCH_FASTER = {}
 
-_LOCK = threading.Lock()
-# (device, raw handle of the caller's stream) -> the hand-over buffer between pairs, grown on demand and kept; LRU, as _ffi._AUX
-_WS = collections.OrderedDict()
+_WS = collections.OrderedDict()                        # (device, stream) -> the hand-over buffer between pairs
 _WS_MAX = 16
 # dispatch counters (tests and tools read them): "hip" / "reference" count residual blocks, the others seams and heads
 CALLS = {"hip": 0, "reference": 0, "seam_hip": 0, "seam_reference": 0, "head_hip": 0, "head_reference": 0}
@@ -81,30 +79,14 @@ def _pack(dims, flat):
 
 
 def _workspace(nbytes, x):
-    """the hand-over buffer of ``x``'s device AND the caller's stream there: the launches of one call write and read it on that
-    stream, so two streams must never see the same one.  A buffer is allocated while its stream is the current one, so the
-    caching allocator hands its memory on only to later work of that same stream: a buffer that growth, the LRU bound or
-    ``release_workspace`` drops while launches still use it is reused behind them, never beside them.  During a graph
-    capture the cache is neither read nor grown: the buffer comes from the graph's own pool and belongs to the graph, which
-    therefore holds no address that a later growth or ``release_workspace`` frees."""
-    n = (nbytes + 3) // 4
-    if x.is_cuda and torch.cuda.is_current_stream_capturing():
-        return torch.empty(n, dtype=torch.float32, device=x.device)
-    key = (str(x.device), _ffi.stream_of(x))
-    with _LOCK:
-        ws = _WS.get(key)
-        if ws is None or ws.numel() < n:
-            ws = _WS[key] = torch.empty(n, dtype=torch.float32, device=x.device)
-            while len(_WS) > _WS_MAX:
-                _WS.popitem(last=False)
-        _WS.move_to_end(key)
-    return ws
+    """the hand-over buffer between pairs, of ``x``'s device and the caller's stream there, by ``_modules.stream_workspace``'s
+    rule: never shared between streams, and during a graph capture neither read nor grown (the buffer then belongs to the graph)"""
+    return stream_workspace(_WS, (nbytes + 3) // 4, x, _WS_MAX)
 
 
 def release_workspace():
     """drop the cached hand-over buffers of every device and stream (2 [B, C, T] activations each at the largest shape seen)"""
-    with _LOCK:
-        _WS.clear()
+    drop_workspaces(_WS)
 
 
 def shape_ok(C, k, dilations):
@@ -292,12 +274,12 @@ def hip_eligible(block, x):
 
 def _reference_block_forward(block, x):
     CALLS["reference"] += 1
-    ref = getattr(type(block), "_reference_forward", None)
-    if ref is not None:
-        return ref(block, x)
-    for c1, c2 in zip(block.convs1, block.convs2):     # a stand-in class without a forward of its own: the same chain
-        x = c2(F.leaky_relu(c1(F.leaky_relu(x, LRELU_SLOPE)), LRELU_SLOPE)) + x
-    return x
+
+    def conv_chain(x):                                 # a stand-in class without a forward of its own: the same chain
+        for c1, c2 in zip(block.convs1, block.convs2):
+            x = c2(F.leaky_relu(c1(F.leaky_relu(x, LRELU_SLOPE)), LRELU_SLOPE)) + x
+        return x
+    return run_reference(block, conv_chain, x)
 
 
 def resblock_forward(block, x):

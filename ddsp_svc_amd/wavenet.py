@@ -25,13 +25,13 @@ form and torch.
 """
 import collections
 import math
-import threading
 
 import torch
 
-from . import _ffi
-from ._modules import drop_workspaces, needs_grad, on_device, packed_table, pad_of, plain, stream_workspace, torch_faster
-from ._patching import park, unpark
+from . import _ffi, _modules
+from ._modules import (FORMS, SPLIT_MAX_TILES, drop_workspaces, needs_grad, on_device, pack_host, packed_table, pad_of,
+                       plain_with_bias, step_biases, stream_workspace)
+from ._patching import patch_forwards, run_reference, unpatch_forwards
 
 SHAPES = ((384, 256), (512, 256))
 # C -> the number of frames B T below which the torch op chain was measured faster on the same GPU (None: at every size; the
@@ -40,8 +40,6 @@ SHAPES = ((384, 256), (512, 256))
 # frames, the kernel at 32 x 862 = 27 584, the smallest size at which it was seen to win (x 1.20 at C = 384, x 1.04 at C = 512),
 # and at 64 x 862 (x 1.18, x 1.04).
 LAYER_TORCH_FASTER = {384: 27584, 512: 27584}
-SPLIT_MAX_TILES = 4096                                 # the split form takes B ceil(T / 16) up to here
-FORMS = ("tiled", "split")
 # C -> the number of frames B T below which the channel-split form (csrc/wavenet_split.h) was MEASURED faster than both the torch
 # chain and the tiled form (tools/wavenet_bench.py --mode split, profiles/wavenet_split_latency.json): the smallest measured size
 # at which it was not the fastest of the three (one past the largest measured size if there is none); no entry where it is not
@@ -53,9 +51,6 @@ SPLIT_BELOW = {384: 8256, 512: 8256}
 # took the split form); separate from conformer.CALLS
 CALLS = {"hip": 0, "reference": 0, "split": 0}
 PACKS = {"count": 0}                                   # weight tables built (a cache hit does not count)
-_LOCK = threading.Lock()
-_STACKED = {}                                          # data_ptrs of the projection weights -> (versions, W [n C, C], b [n C], kept)
-_STACKED_MAX = 16
 _WS = collections.OrderedDict()                        # (device, stream) -> the buffer the split form's gate passes through
 _WS_MAX = 8
 
@@ -71,17 +66,15 @@ def split_tile(C, H):
 
 
 def split_in_range(B, T):
-    """the split form takes ``B ceil(T / 16)`` tiles up to ``SPLIT_MAX_TILES``"""
-    return B * -(-T // 16) <= SPLIT_MAX_TILES
+    """the split form takes ``B ceil(T / 16)`` tiles up to ``SPLIT_MAX_TILES`` (``_modules.split_in_range``)"""
+    return _modules.split_in_range(B, T)
 
 
 def choose_form(C, B, T):
     """where the hook sends a layer call of ``B x T`` frames: ``"split"`` within the split form's range below the measured
-    ``SPLIT_BELOW[C]``, else ``"tiled"`` unless ``LAYER_TORCH_FASTER`` gives the size to torch, else None (the torch chain).
-    The two forms give the same bits, so the choice never shows in a result."""
-    if C in SPLIT_BELOW and split_in_range(B, T) and B * T < SPLIT_BELOW[C]:
-        return "split"
-    return None if torch_faster(LAYER_TORCH_FASTER, C, B * T) else "tiled"
+    ``SPLIT_BELOW[C]``, else ``"tiled"`` unless ``LAYER_TORCH_FASTER`` gives the size to torch, else None (the torch chain):
+    ``_modules.choose_form`` on this module's two tables as they are now"""
+    return _modules.choose_form(SPLIT_BELOW, LAYER_TORCH_FASTER, C, B, T)
 
 
 def _workspace(B, T, C, x):
@@ -98,14 +91,9 @@ def release_workspace():
 
 def _pack(dims, flat):
     """the host table of ``(wdil, bdil, wc, bc, wo, bo)``, for ``packed_table``"""
-    (C, H), lib = dims, _ffi.lib()
-    nbytes = int(lib.ddsp_hip_wavenet_layer_pack_bytes(C, H))
-    if nbytes == 0:
-        raise ValueError("residual_layer: (C, H) = (%d, %d) is outside the kernel's range" % (C, H))
-    with torch.no_grad():
-        staged = [t.detach().to("cpu", torch.float32).contiguous() for t in flat]
-    host = torch.empty(nbytes // 4, dtype=torch.float32)
-    _ffi.check(lib.ddsp_hip_wavenet_layer_pack(*[t.data_ptr() for t in staged], C, H, host.data_ptr(), nbytes))
+    lib = _ffi.lib()
+    refusal = "residual_layer: (C, H) = (%d, %d) is outside the kernel's range" % dims
+    host = pack_host(int(lib.ddsp_hip_wavenet_layer_pack_bytes(*dims)), refusal, flat, lib.ddsp_hip_wavenet_layer_pack, dims)
     PACKS["count"] += 1
     return host
 
@@ -151,7 +139,7 @@ def residual_layer(x, cond, d, weights, out=None, skip=None, accumulate=False, f
         raise ValueError("residual_layer: T must be positive")
     if form not in FORMS:
         raise ValueError("residual_layer: form must be 'tiled' or 'split'")
-    if form == "split" and not split_in_range(B, T):
+    if form == "split" and not _modules.split_in_range(B, T):
         raise ValueError("residual_layer: the split form takes B ceil(T / 16) <= %d tiles" % SPLIT_MAX_TILES)
     if out is x or skip is x or (out is not None and out is skip):
         raise ValueError("residual_layer: out and skip must be two tensors, neither of them x")
@@ -180,25 +168,6 @@ def residual_layer(x, cond, d, weights, out=None, skip=None, accumulate=False, f
     return y, s
 
 
-def _stacked_projection(projs):
-    """``(W [n C, C], b [n C])``: the layers' ``(weight [C, C], bias [C])`` step projections stacked, cached by the rule of
-    ``_modules.packed_table`` (found again by every tensor's ``data_ptr``, a hit while every ``_version`` is unchanged)"""
-    flat = [t for p in projs for t in p]
-    key = tuple(t.data_ptr() for t in flat)
-    versions = tuple(t._version for t in flat)
-    with _LOCK:
-        hit = _STACKED.get(key)
-        if hit is not None and hit[0] == versions:
-            return hit[1], hit[2]
-        with torch.no_grad():
-            W = torch.cat([p[0].detach() for p in projs], 0).contiguous()
-            b = torch.cat([p[1].detach() for p in projs], 0).contiguous()
-        while len(_STACKED) >= _STACKED_MAX:
-            _STACKED.pop(next(iter(_STACKED)))
-        _STACKED[key] = (versions, W, b, flat)
-    return W, b
-
-
 def residual_stack(x, cond, s, layers, form="tiled"):
     """The residual layers of a WaveNet: ``x [B, C, T]``, ``cond [B, H, T]``, ``s [B, C]`` (the step embedding after the mlp),
     ``layers`` a list of ``(weights, (wp [C, C], bp [C]))``.  The projections of all layers are ONE matmul; then one launch per
@@ -207,11 +176,10 @@ def residual_stack(x, cond, s, layers, form="tiled"):
     layers (in a graph capture as well).  Returns ``(x after the last layer, the sum of the skips)``."""
     if not layers:
         raise ValueError("residual_stack: no layers")
-    if form not in FORMS or (form == "split" and (x.dim() != 3 or not split_in_range(x.shape[0], x.shape[2]))):
+    if form not in FORMS or (form == "split" and (x.dim() != 3 or not _modules.split_in_range(x.shape[0], x.shape[2]))):
         raise ValueError("residual_stack: form must be 'tiled' or 'split', the latter with B ceil(T / 16) <= %d" % SPLIT_MAX_TILES)
     n, C = len(layers), x.shape[1]
-    W, b = _stacked_projection([p for _, p in layers])
-    d = torch.addmm(b, s, W.t()).view(s.shape[0], n, C).transpose(0, 1).contiguous()     # [n, B, C]
+    d = step_biases(s, [p for _, p in layers])                                            # [n, B, C]
     cond = cond.contiguous()
     bufs = (torch.empty_like(x, memory_format=torch.contiguous_format),
             torch.empty_like(x, memory_format=torch.contiguous_format) if n > 1 else None)
@@ -227,13 +195,8 @@ def residual_stack(x, cond, s, layers, form="tiled"):
 
 # ---- the reference's modules --------------------------------------------------------------------------------------------------
 
-def _plain(m):
-    """``_modules.plain`` and a bias that is a plain float32 parameter too"""
-    return plain(m) and isinstance(m._parameters.get("bias"), torch.Tensor) and m.bias.dtype == torch.float32
-
-
 def _conv(c, cin, cout, k, pad):
-    return (isinstance(c, torch.nn.Conv1d) and _plain(c) and c.in_channels == cin and c.out_channels == cout
+    return (isinstance(c, torch.nn.Conv1d) and plain_with_bias(c) and c.in_channels == cin and c.out_channels == cout
             and c.kernel_size == (k,) and c.stride == (1,) and c.dilation == (1,) and c.groups == 1 and pad_of(c) == (pad,)
             and c.padding_mode == "zeros")
 
@@ -251,7 +214,7 @@ def _layer_spec(block):
         return None
     if not _conv(dil, C, 2 * C, 3, 1) or not _conv(cp, H, 2 * C, 1, 0) or not _conv(op, C, 2 * C, 1, 0):
         return None
-    if not isinstance(proj, torch.nn.Linear) or not _plain(proj) or proj.in_features != C or proj.out_features != C:
+    if not isinstance(proj, torch.nn.Linear) or not plain_with_bias(proj) or proj.in_features != C or proj.out_features != C:
         return None
     return (dil.weight, dil.bias, cp.weight, cp.bias, op.weight, op.bias), (proj.weight, proj.bias)
 
@@ -281,10 +244,7 @@ def layer_eligible(block, x, cond, s):
 
 def _reference_layer_forward(block, x, conditioner, diffusion_step):
     CALLS["reference"] += 1
-    ref = getattr(type(block), "_reference_forward", None)
-    if ref is not None:
-        return ref(block, x, conditioner, diffusion_step)
-    return block.reference_forward(x, conditioner, diffusion_step)
+    return run_reference(block, getattr(block, "reference_forward", None), x, conditioner, diffusion_step)
 
 
 def layer_forward(block, x, conditioner, diffusion_step):
@@ -319,38 +279,17 @@ def net_forward(wavenet, spec, diffusion_step, cond):
 
 
 _REFERENCE_MODULE = "diffusion.wavenet"
-
-
-def _block_forward(self, x, conditioner, diffusion_step):
-    return layer_forward(self, x, conditioner, diffusion_step)
-
-
-def _wavenet_forward(self, spec, diffusion_step, cond):
-    return net_forward(self, spec, diffusion_step, cond)
+_CLASSES = (("ResidualBlock", lambda self, x, conditioner, diffusion_step: layer_forward(self, x, conditioner, diffusion_step)),
+            ("WaveNet", lambda self, spec, diffusion_step, cond: net_forward(self, spec, diffusion_step, cond)))
 
 
 def patch_reference_wavenet():
     """Route ``ResidualBlock.forward`` and ``WaveNet.forward`` of ``diffusion.wavenet`` through the dispatchers above.
     Idempotent; returns the module, or None when it does not import.  ``vocoder.patch_reference()`` does not call it: the hook
     is opt-in."""
-    import importlib
-    try:
-        mod = importlib.import_module(_REFERENCE_MODULE)
-    except Exception:                                  # not importable here: nothing to patch
-        return None
-    for cls_name, fwd in (("ResidualBlock", _block_forward), ("WaveNet", _wavenet_forward)):
-        cls = getattr(mod, cls_name, None)
-        if cls is not None and cls.forward is park(cls, "forward"):
-            cls.forward = fwd
-    return mod
+    return (patch_forwards([_REFERENCE_MODULE], _CLASSES) or [None])[0]
 
 
 def unpatch_reference_wavenet():
     """Undo ``patch_reference_wavenet()``."""
-    import sys
-    mod = sys.modules.get(_REFERENCE_MODULE)
-    if mod is None:
-        return
-    for cls_name in ("ResidualBlock", "WaveNet"):
-        if hasattr(mod, cls_name):
-            unpark(getattr(mod, cls_name), "forward")
+    unpatch_forwards([_REFERENCE_MODULE], [name for name, _ in _CLASSES])
