@@ -6,7 +6,9 @@ routes a size to the split form, the tiled form or torch.  ``mel`` uses ``needs_
 The cache rule: a table is found again by the device, the kind of kernel, the shape integers and the ``data_ptr`` of every
 parameter tensor; it is a hit only while every tensor's ``_version`` is the one it was packed at (an in-place write packs
 again); the entry keeps the tensors alive, so a ``data_ptr`` cannot come back as another tensor's; all kinds share one bound of
-``_PACKED_MAX`` entries, dropped oldest first; lookup, pack and insert happen under one lock.
+``_PACKED_MAX`` entries, dropped oldest first; lookup, pack and insert happen under one lock.  An inference tensor (made inside
+``torch.inference_mode()``) has no ``_version``, so a write to it cannot be seen: a key that holds one is never served or stored,
+its table is packed on every call (``versions_of`` is the one place that decides this and the only reader of ``_version``).
 """
 import threading
 
@@ -19,12 +21,38 @@ _PACKED = {}                                           # key -> (versions, devic
 _PACKED_MAX = 256
 
 
+def tracked(*tensors):
+    """none of ``tensors`` (None entries skipped) is an inference tensor: every one has a ``_version`` that shows a write"""
+    return not any(t is not None and t.is_inference() for t in tensors)
+
+
+def versions_of(tensors):
+    """every tensor's ``_version`` -- what a cache entry is a hit by --, or None when one of them is an inference tensor, which
+    has none: nothing made from such tensors is served from a cache or stored in one"""
+    return tuple([t._version for t in tensors]) if tracked(*tensors) else None
+
+
+def autocast_on(x):
+    """autocast is enabled for ``x``'s device type: a module hook then leaves the call to the module's own forward, whose torch
+    ops return autocast's dtypes (the float32 kernels would not); the functional forms compute in float32 regardless"""
+    return torch.is_autocast_enabled(x.device.type)
+
+
+def no_autocast(x):
+    """the context in which the torch ops of a functional form (an ``addmm``, a ``linear``) stay float32 inside a caller's
+    autocast region for ``x``'s device type"""
+    return torch.autocast(x.device.type, enabled=False)
+
+
 def packed_table(kind, dims, tensors, device, pack):
     """the float32 table on ``device`` that ``pack(dims, tensors)`` -- the caller's own function, run only when the cache misses:
     it sizes the host table with its C ``*_pack_bytes`` entry, stages its operands and fills it with its C ``*_pack`` entry --
     returns for ``tensors``; cached by the rule above"""
+    versions = versions_of(tensors)
+    if versions is None:
+        with _LOCK:
+            return pack(dims, tensors).to(device)
     key = (str(device), kind, *dims, *[t.data_ptr() for t in tensors])
-    versions = tuple([t._version for t in tensors])
     with _LOCK:
         hit = _PACKED.get(key)
         if hit is not None and hit[0] == versions:
@@ -62,17 +90,23 @@ _STACKED_MAX = 32                                      # for both denoisers: as 
 def stacked_projection(projs):
     """``(W [n C, C], b [n C])``: the layers' ``(weight [C, C] or [C, C, 1], bias [C])`` step projections stacked, cached by the
     rule of ``packed_table`` (found again by every tensor's ``data_ptr``, a hit while every ``_version`` is unchanged, the entry
-    keeps the tensors alive, ``_STACKED_MAX`` entries dropped oldest first, under the same lock)"""
+    keeps the tensors alive, ``_STACKED_MAX`` entries dropped oldest first, under the same lock; stacked on every call, never
+    stored, when one of them is an inference tensor)"""
     flat = [t for p in projs for t in p]
+
+    def stack():
+        with torch.no_grad():
+            return (torch.cat([p[0].detach().reshape(p[0].shape[0], -1) for p in projs], 0).contiguous(),
+                    torch.cat([p[1].detach() for p in projs], 0).contiguous())
+    versions = versions_of(flat)
+    if versions is None:
+        return stack()
     key = tuple(t.data_ptr() for t in flat)
-    versions = tuple(t._version for t in flat)
     with _LOCK:
         hit = _STACKED.get(key)
         if hit is not None and hit[0] == versions:
             return hit[1], hit[2]
-        with torch.no_grad():
-            W = torch.cat([p[0].detach().reshape(p[0].shape[0], -1) for p in projs], 0).contiguous()
-            b = torch.cat([p[1].detach() for p in projs], 0).contiguous()
+        W, b = stack()
         while len(_STACKED) >= _STACKED_MAX:
             _STACKED.pop(next(iter(_STACKED)))
         _STACKED[key] = (versions, W, b, flat)
@@ -82,7 +116,8 @@ def stacked_projection(projs):
 def step_biases(s, projs):
     """``d [n, B, C]``: the step embedding ``s [B, C]`` through all n layers' projections in ONE matmul"""
     W, b = stacked_projection(projs)
-    return torch.addmm(b, s, W.t()).view(s.shape[0], len(projs), W.shape[1]).transpose(0, 1).contiguous()
+    with no_autocast(s):
+        return torch.addmm(b, s, W.t()).view(s.shape[0], len(projs), W.shape[1]).transpose(0, 1).contiguous()
 
 
 _WS_LOCK = threading.Lock()
@@ -136,9 +171,12 @@ def pad_of(conv):
 
 def plain(module):
     """``weight`` is a plain float32 parameter and the module carries no hook (a weight-norm hook recomputes ``weight``; any other
-    expects the module's own forward to run).  What a call site asks of the bias it asks itself."""
+    expects the module's own forward to run); neither it nor a bias is an inference tensor (a module built or loaded inside
+    ``inference_mode`` runs its own forward: cheaper than a table packed and copied to the device on every call).  What else a
+    call site asks of the bias it asks itself."""
     return (isinstance(module._parameters.get("weight"), torch.Tensor) and not module._forward_pre_hooks
-            and not module._forward_hooks and module.weight.dtype == torch.float32)
+            and not module._forward_hooks and module.weight.dtype == torch.float32
+            and tracked(module.weight, module._parameters.get("bias")))
 
 
 def plain_with_bias(module):

@@ -15,10 +15,11 @@ Dispatch is decided from a module's structure, not its class.  ``fast_eligible``
 ``projection_matrix [266, 64]`` on q's device, not ``causal``, not ``generalized_attention``, not ``no_projection``, ``v`` given.
 ``self_eligible``: ``local_attn is None``, ``global_heads == heads``, four plain hook-free float32 ``nn.Linear`` with biases
 (``to_q``, ``to_k``, ``to_v``: any width to ``heads * 64``), the dropout inactive, no context and no mask, and a ``fast_attention``
-that is eligible itself.  Both: float32 tensors on the GPU and no gradient needed.  Everything else -- a mask, cross-attention,
-local heads, other head widths, training, CPU tensors, bf16 -- runs the reference's own forward.  ``normalize`` is read at call
-time from ``FLAG_PCMER_NORM`` of the module that defines the class.  ``ATTN_TORCH_FASTER`` maps the head width to the number of
-frames B N below which the same-GPU torch chain was measured faster (tools/attention_bench.py).
+that is eligible itself.  Both: float32 tensors on the GPU, no gradient needed, autocast off, no weight or projection matrix that
+is an inference tensor.  Everything else -- a mask, cross-attention, local heads, other head widths, training, CPU tensors, bf16 --
+runs the reference's own forward.  ``normalize`` is read at call time from ``FLAG_PCMER_NORM`` of the module that defines the
+class.  ``ATTN_TORCH_FASTER`` maps the head width to the number of frames B N below which the same-GPU torch chain was measured
+faster (tools/attention_bench.py).
 """
 import collections
 import sys
@@ -27,8 +28,8 @@ import torch
 import torch.nn.functional as F
 
 from . import _ffi
-from ._modules import (drop_workspaces, needs_grad, on_device, pack_host, packed_table, plain_with_bias, stream_workspace,
-                       torch_faster)
+from ._modules import (autocast_on, drop_workspaces, needs_grad, no_autocast, on_device, pack_host, packed_table,
+                       plain_with_bias, stream_workspace, torch_faster, tracked)
 from ._patching import patch_forwards, run_reference, unpatch_forwards
 
 DIM_HEAD = 64
@@ -152,10 +153,11 @@ def self_attention(x, wq, bq, wk, bk, wv, bv, wo, bo, projection, heads=8, norma
         raise ValueError("self_attention: to_out must be [Dout, heads * 64]")
     cat = packed_table("performer_qkv", (D, inner), [wq, wk, wv, bq, bk, bv], x.device, _cat)
     w, b = cat[:D * 3 * inner].view(D, 3 * inner), cat[D * 3 * inner:]
-    qkv = torch.addmm(b, x.reshape(B * N, D), w).view(B, N, 3, heads, DIM_HEAD)
-    q, k, v = (qkv[:, :, i].permute(0, 2, 1, 3) for i in range(3))
-    y = fast_attention(q, k, v, projection, normalize=normalize)
-    return F.linear(y.permute(0, 2, 1, 3).reshape(B, N, inner), wo, bo)
+    with no_autocast(x):                               # float32 inside a caller's autocast region too: the kernels take no other
+        qkv = torch.addmm(b, x.reshape(B * N, D), w).view(B, N, 3, heads, DIM_HEAD)
+        q, k, v = (qkv[:, :, i].permute(0, 2, 1, 3) for i in range(3))
+        y = fast_attention(q, k, v, projection, normalize=normalize)
+        return F.linear(y.permute(0, 2, 1, 3).reshape(B, N, inner), wo, bo)
 
 
 # ---- the reference's modules --------------------------------------------------------------------------------------------------
@@ -175,7 +177,7 @@ def _fast_spec(module, device):
         return None
     proj = getattr(module, "projection_matrix", None)
     if (getattr(module, "dim_heads", None) != DIM_HEAD or not isinstance(proj, torch.Tensor) or proj.dtype != torch.float32
-            or tuple(proj.shape) != (FEATURES, DIM_HEAD) or proj.device != device):
+            or tuple(proj.shape) != (FEATURES, DIM_HEAD) or proj.device != device or not tracked(proj)):
         return None
     if getattr(module, "causal", True) or getattr(module, "generalized_attention", True) or getattr(module, "no_projection", True):
         return None
@@ -184,7 +186,7 @@ def _fast_spec(module, device):
 
 def fast_eligible(module, q, k, v):
     """the projection matrix to run ``module`` (a ``FastAttention``) on q, k, v with the HIP kernels, or None: its own forward"""
-    if v is None or not (on_device(q, 4) and on_device(k, 4) and on_device(v, 4)):
+    if v is None or not (on_device(q, 4) and on_device(k, 4) and on_device(v, 4)) or autocast_on(q):
         return None
     proj = _fast_spec(module, q.device)
     if proj is None:
@@ -206,7 +208,7 @@ def self_eligible(module, x, context=None, mask=None, context_mask=None):
     """the arguments of ``self_attention`` after ``x`` to run ``module`` (a ``SelfAttention``) on the HIP kernels, or None"""
     if context is not None or mask is not None or context_mask is not None or not on_device(x, 3) or x.shape[1] < 1:
         return None
-    if not isinstance(module, torch.nn.Module) or _hooked(module):
+    if autocast_on(x) or not isinstance(module, torch.nn.Module) or _hooked(module):
         return None
     heads, fast = getattr(module, "heads", None), getattr(module, "fast_attention", None)
     if (not isinstance(heads, int) or heads < 1 or getattr(module, "local_attn", True) is not None

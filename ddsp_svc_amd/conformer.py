@@ -12,14 +12,16 @@ pointwise convolutions as f32 MFMA GEMMs, the GLU, the 31-tap depthwise convolut
 Dispatch (``conv_eligible``) is decided from a module's structure, not its class: a ``net`` Sequential of ``[LayerNorm(D) |
 Identity, Transpose, Conv1d(D, 4 D, 1), GLU(dim=1), depthwise Conv1d(2 D, 2 D, 31, padding 15, groups 2 D) or pcmer's pad-then-conv
 wrapper, SiLU | Swish, Conv1d(2 D, D, 1), Transpose, Dropout]`` with D = 256, plain float32 parameters without hooks, the
-dropout inactive, a float32 ``[B, L, 256]`` tensor on the GPU and no gradient needed.  Everything else -- D = 512, other tap
-counts, weight norm, training, CPU tensors -- runs the module's own ``net``.  ``CONV_TORCH_FASTER`` maps D to the number of frames
-B L below which the same-GPU torch chain was measured faster (tools/conformer_bench.py).
+dropout inactive, a float32 ``[B, L, 256]`` tensor on the GPU, no gradient needed and autocast off.  Everything else -- D = 512,
+other tap counts, weight norm, training, CPU tensors, parameters that are inference tensors -- runs the module's own ``net``.
+``CONV_TORCH_FASTER`` maps D to the number of frames B L below which the same-GPU torch chain was measured faster
+(tools/conformer_bench.py).
 """
 import torch
 
 from . import _ffi
-from ._modules import needs_grad, on_device, pack_host, packed_table, pad_of, plain_with_bias, pointwise, torch_faster
+from ._modules import (autocast_on, needs_grad, on_device, pack_host, packed_table, pad_of, plain_with_bias, pointwise,
+                       torch_faster, tracked)
 from ._patching import patch_forwards, run_reference, unpatch_forwards
 
 DIMS = (256,)
@@ -148,7 +150,8 @@ def _conv_spec(module):
     D = c1.in_channels
     if isinstance(ln, torch.nn.LayerNorm):
         if (tuple(ln.normalized_shape) != (D,) or not ln.elementwise_affine or ln.weight is None or ln.bias is None
-                or ln.weight.dtype != torch.float32 or ln._forward_pre_hooks or ln._forward_hooks):
+                or ln.weight.dtype != torch.float32 or ln._forward_pre_hooks or ln._forward_hooks
+                or not tracked(ln.weight, ln.bias)):
             return None
         norm, eps = (ln.weight, ln.bias), ln.eps
     elif isinstance(ln, torch.nn.Identity):
@@ -173,7 +176,7 @@ def _conv_spec(module):
 
 def conv_eligible(module, x):
     """the ``(weights, norm, eps)`` to run ``module`` on ``x`` with the HIP kernel, or None: the module's own ``net``"""
-    if not on_device(x, 3) or x.shape[1] < 1:
+    if not on_device(x, 3) or x.shape[1] < 1 or autocast_on(x):
         return None
     spec = _conv_spec(module)
     if spec is None:

@@ -15,7 +15,8 @@ and the residual -- with the GLU's output handed over through a workspace.  f32 
 Dispatch (``layer_eligible``) is decided from a module's structure, not its class: ``attn is None``, ``wavenet_like_proj is
 None``, a ``conformer`` that is the conv chain of ``conformer._conv_spec`` without LayerNorm and with an inactive dropout, a
 ``diffusion_step_projection`` ``Conv1d(D, D, 1)`` and a ``condition_projection`` ``Conv1d(Hc, D, 1)``, plain float32 parameters
-without hooks, float32 tensors on the GPU, no gradient needed, autocast off, (D, Hc) = (512, 128).  Everything else runs the
+without hooks and none of them an inference tensor, float32 tensors on the GPU, no gradient needed, autocast off, (D, Hc) =
+(512, 128).  Everything else runs the
 module's own forward.  ``LAYER_TORCH_FASTER`` maps D to the number of frames B L below which the same-GPU torch chain was
 measured faster (tools/naive_v2_bench.py); None: at every size, which is also what a D without a committed
 measurement gets.
@@ -32,8 +33,8 @@ import torch.nn.functional as F
 
 from . import _ffi, _modules
 from . import conformer as _conformer
-from ._modules import (FORMS, SPLIT_MAX_TILES, drop_workspaces, needs_grad, on_device, pack_host, packed_table, pointwise,
-                       step_biases, stream_workspace)
+from ._modules import (FORMS, SPLIT_MAX_TILES, autocast_on, drop_workspaces, needs_grad, on_device, pack_host, packed_table,
+                       pointwise, step_biases, stream_workspace)
 from ._patching import patch_forwards, run_reference, unpatch_forwards
 
 SHAPES = ((512, 128),)
@@ -219,7 +220,7 @@ def layer_eligible(layer, x, cond, step):
     with the HIP kernels (in the form ``choose_form`` names for the size), or None: the layer's own forward"""
     if not on_device(x, 3) or not on_device(cond, 3) or not on_device(step, 3) or x.shape[2] < 1:
         return None
-    if torch.is_autocast_enabled(x.device.type):
+    if autocast_on(x):
         return None
     spec = _layer_spec(layer)
     if spec is None:
@@ -263,7 +264,7 @@ def _stack_candidate(net, spec, cond):
     layers = list(net.residual_layers)
     if not layers or net.mask_cond_ratio is not None or getattr(net, "wavenet_like", False):
         return False
-    if not (on_device(spec, 3) or on_device(spec, 4)) or not on_device(cond, 3) or torch.is_autocast_enabled(spec.device.type):
+    if not (on_device(spec, 3) or on_device(spec, 4)) or not on_device(cond, 3) or autocast_on(spec):
         return False
     specs = [_layer_spec(layer) for layer in layers]
     if any(sp is None for sp in specs) or needs_grad([spec, cond] + list(net.parameters())):

@@ -12,7 +12,7 @@ f32 MFMA GEMMs with the intermediate in LDS, and the ``xs / num_kernels`` sum fo
   unpatch_reference_generator
   release_workspace, clear_packed   drop the cached hand-over buffers / the cached weight tables (``_modules``)
 
-Dispatch (``hip_eligible``): a float32 tensor on the GPU, no gradient needed, C in {16, 32, 64}, k in {3, 7, 11}, dilations the
+Dispatch (``hip_eligible``): a float32 tensor on the GPU, no gradient needed, autocast off, C in {16, 32, 64}, k in {3, 7, 11}, dilations the
 kernel's LDS image holds, and plain ``Conv1d`` weights -- every conv of the block has had ``remove_weight_norm`` applied (the
 weight-norm hook recomputes ``weight`` in a forward pre-hook, which a call that bypasses ``Conv1d.forward`` would never run).
 Everything else -- 128 / 256 channels, ``ResBlock2``, training, CPU tensors -- takes the reference's own forward unchanged.
@@ -32,8 +32,8 @@ import torch
 import torch.nn.functional as F
 
 from . import _ffi
-from ._modules import (clear_packed, drop_workspaces, needs_grad, on_device, packed_table, pad_of, plain,  # noqa: F401
-                       stream_workspace, torch_faster)
+from ._modules import (autocast_on, clear_packed, drop_workspaces, needs_grad, on_device, packed_table, pad_of,  # noqa: F401
+                       plain, stream_workspace, torch_faster)
 from ._patching import park, run_reference, unpark
 
 CHANNELS = (16, 32, 64)
@@ -262,7 +262,7 @@ def _block_spec(block):
 
 def hip_eligible(block, x):
     """the ``(weights, dilations)`` to run ``block`` on ``x`` with the HIP kernel, or None: the reference's forward"""
-    if not on_device(x, 3) or x.shape[-1] < 1:
+    if not on_device(x, 3) or x.shape[-1] < 1 or autocast_on(x):
         return None
     spec = _block_spec(block)
     if spec is None or x.shape[1] != spec[0][0][0].shape[0]:
@@ -332,7 +332,7 @@ def _seam_spec(up, noise_conv):
 
 def seam_eligible(up, noise_conv, x, source):
     """``(Cout, u, s)`` to run ``up(lrelu(x)) + noise_conv(source)`` with the HIP kernel, or None: the torch line"""
-    if not on_device(x, 3) or x.shape[-1] < 1:
+    if not on_device(x, 3) or x.shape[-1] < 1 or autocast_on(x):
         return None
     if not isinstance(source, torch.Tensor) or source.dtype != torch.float32 or source.dim() != 3 or source.device != x.device:
         return None
@@ -360,7 +360,7 @@ def seam_forward(up, noise_conv, x, source):
 
 def head_eligible(conv_post, x):
     """True to run ``tanh(conv_post(lrelu(x)))`` with the HIP kernel"""
-    if not on_device(x, 3) or x.shape[-1] < 1:
+    if not on_device(x, 3) or x.shape[-1] < 1 or autocast_on(x):
         return False
     if not _plain_module(conv_post, torch.nn.Conv1d):
         return False

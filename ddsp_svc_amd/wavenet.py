@@ -13,7 +13,7 @@ as f32 MFMA GEMMs, the gate between them on the CU, the skip sum accumulated in 
 Dispatch (``layer_eligible``) is decided from a module's structure, not its class: a ``dilated_conv`` ``Conv1d(C, 2 C, 3,
 padding 1, dilation 1)`` with zeros padding, a ``conditioner_projection`` ``Conv1d(H, 2 C, 1)``, an ``output_projection``
 ``Conv1d(C, 2 C, 1)`` and a ``diffusion_projection`` ``Linear(C, C)``, plain float32 parameters without hooks, float32 tensors on
-the GPU, no gradient needed, autocast off, (C, H) = (384, 256) or (512, 256).  Everything else runs the module's own forward.
+the GPU, no gradient needed, autocast off, no parameter an inference tensor, (C, H) = (384, 256) or (512, 256).  Everything else runs the module's own forward.
 ``LAYER_TORCH_FASTER`` maps C to the number of frames B T below which the same-GPU torch chain was measured faster
 (tools/wavenet_bench.py); None: at every size, which is also what a C without a committed measurement gets.
 
@@ -29,8 +29,8 @@ import math
 import torch
 
 from . import _ffi, _modules
-from ._modules import (FORMS, SPLIT_MAX_TILES, drop_workspaces, needs_grad, on_device, pack_host, packed_table, pad_of,
-                       plain_with_bias, step_biases, stream_workspace)
+from ._modules import (FORMS, SPLIT_MAX_TILES, autocast_on, drop_workspaces, needs_grad, on_device, pack_host, packed_table,
+                       pad_of, plain_with_bias, step_biases, stream_workspace)
 from ._patching import patch_forwards, run_reference, unpatch_forwards
 
 SHAPES = ((384, 256), (512, 256))
@@ -224,7 +224,7 @@ def layer_eligible(block, x, cond, s):
     the size), or None: the block's own forward"""
     if not on_device(x, 3) or not on_device(cond, 3) or not on_device(s, 2) or x.shape[2] < 1:
         return None
-    if torch.is_autocast_enabled(x.device.type):
+    if autocast_on(x):
         return None
     spec = _layer_spec(block)
     if spec is None:
