@@ -95,6 +95,12 @@ __device__ __forceinline__ float div_pos(float a, float b);   // a / b, b > 0 (b
 // Phase bookkeeping shared by the scan kernels and every consumer that re-derives x[t].
 // infer != 0: terms and running sum in float64 (vocoder.py:566); infer == 0: float32 terms, float64
 // running sum rounded to float32 per output as ATen's CPU cumsum does, then float32 wrap (vocoder.py:568).
+// Under infer, in the shift form of the interpolation (hop a power of two up to 512), the consumers (the frame totals of phase.hip,
+// frame_phase() and the rebuilds inlined in exciter.hip) do not divide per sample: they accumulate double(f0u) -- float32 values,
+// whose float64 sum over a frame is exact unless magnitudes 2^29 apart meet in it -- and multiply the SUM by rsr_d once,
+// x = fma(S, rsr_d, base) (scaled()).  Against the sum of the correctly rounded quotients that moves a frame's phase by ~1e-15
+// cycles, where a float32 x resolves 3e-8.  term() is the quotient of ONE sample: the infer == 0 path, the general
+// interpolation, and the sample at a frame's start behind phase_frames.
 struct PhaseCfg {
   double sr_d;
   double rsr_d;            // RN(1 / sr)
@@ -112,6 +118,13 @@ struct PhaseCfg {
     const double e = fma(-q0, sr_d, a);
     return fma(e, rsr_d, q0);
   }
+  // infer: the running sum S of double(f0u) in cycles on top of base, and a frame's start value with the initial phase on it
+  __device__ __forceinline__ double scaled(double S, double base) const { return fma(S, rsr_d, base); }
+  __device__ __forceinline__ double with_ip(double base, float ip) const {
+    return has_ip ? base + ((double)ip / 2.0) / kPiD : base;
+  }
+  // infer: unwrapped phase in cycles (initial phase included) -> wrapped float32 x
+  __device__ __forceinline__ float wrap_cycles(double x) const { return (float)(x - rint(x)); }
   // running (unwrapped) sum P in cycles -> wrapped float32 x, vocoder.py:569-572
   __device__ __forceinline__ float wrap(double P, float ip) const {
     if (infer) {

@@ -241,15 +241,28 @@ __global__ void __launch_bounds__(256) k_sins_bank3(const float* __restrict__ f0
   const Upsampler::Row3 rows = up.load3(f0_row, f);
   const float ip = cfg.has_ip ? initial_phase[b] : 0.0f;
   const long t0 = (long)f * HOP + 2 * tid;
-  const double q0 = cfg.term(up.at3_pow2(rows, 2 * tid));       // the launcher has checked up.shift > 0 (hop 512, F hop <= 2^24)
-  const double q1 = cfg.term(up.at3_pow2(rows, 2 * tid + 1));
+  const float v0 = up.at3_pow2(rows, 2 * tid);                  // the launcher has checked up.shift > 0 (hop 512, F hop <= 2^24)
+  const float v1 = up.at3_pow2(rows, 2 * tid + 1);
+  // infer (workgroup-uniform): the samples themselves are summed and the sum scaled once (PhaseCfg); else the quotients
+  const double q0 = cfg.infer ? (double)v0 : cfg.term(v0);
+  const double q1 = cfg.infer ? (double)v1 : cfg.term(v1);
   const double mine = q0 + q1;
   const double excl = wave_excl_scan(mine, lane);
   if (lane == 63) wsum[wave] = excl + mine;
   __syncthreads();                                  // also publishes amp[]
-  double base = phase0[fr] + excl;
-  for (int w = 0; w < wave; ++w) base += wsum[w];
-  const float xa = cfg.wrap(base + q0, ip), xb = cfg.wrap(base + q0 + q1, ip);
+  float xa, xb;
+  if (cfg.infer) {
+    double before = excl;
+    for (int w = 0; w < wave; ++w) before += wsum[w];
+    const double base = cfg.with_ip(cfg.scaled(before, phase0[fr]), ip);
+    xa = cfg.wrap_cycles(cfg.scaled(q0, base));
+    xb = cfg.wrap_cycles(cfg.scaled(mine, base));
+  } else {
+    double base = phase0[fr] + excl;
+    for (int w = 0; w < wave; ++w) base += wsum[w];
+    xa = cfg.wrap(base + q0, ip);
+    xb = cfg.wrap(base + q0 + q1, ip);
+  }
   const f32x2 theta = {kTwoPiF * xa, kTwoPiF * xb};                       // vocoder.py:574
   // table cis(j theta), j = 1..8, as (cos_A, cos_B) / (sin_A, sin_B) pairs; the block-to-block rotation cis(17 theta)
   f32x2 tc[SB3_J], ts[SB3_J];
@@ -350,19 +363,33 @@ __global__ void __launch_bounds__(64) k_sins_bank_bwd_mfma(const float* __restri
     const float ip = cfg.has_ip ? initial_phase[b] : 0.0f;
     double pre[SPL];
     double acc = 0.0;
+    float xs[SPL];
+    if (cfg.infer) {                                            // workgroup-uniform: as frame_phase() (frame_phase.h)
 #pragma unroll
-    for (int r = 0; r < SPL; ++r) {
-      acc += cfg.term(up.at3_pow2(rows, lane * SPL + r));       // the launcher has checked up.shift > 0
-      pre[r] = acc;
+      for (int r = 0; r < SPL; ++r) {
+        acc += (double)up.at3_pow2(rows, lane * SPL + r);       // the launcher has checked up.shift > 0
+        pre[r] = acc;
+      }
+      const double base = cfg.with_ip(cfg.scaled(wave_excl_scan(acc, lane), phase0[fr]), ip);
+#pragma unroll
+      for (int r = 0; r < SPL; ++r) xs[r] = cfg.wrap_cycles(cfg.scaled(pre[r], base));
+    } else {
+#pragma unroll
+      for (int r = 0; r < SPL; ++r) {
+        acc += cfg.term(up.at3_pow2(rows, lane * SPL + r));
+        pre[r] = acc;
+      }
+      const double base = phase0[fr] + wave_excl_scan(acc, lane);
+#pragma unroll
+      for (int r = 0; r < SPL; ++r) xs[r] = cfg.wrap(base + pre[r], ip);
     }
-    const double base = phase0[fr] + wave_excl_scan(acc, lane);
     const float* gp = grad_out + b * (long)F * HOP + (long)f * HOP + lane * SPL;
 #pragma unroll
     for (int r = 0; r < SPL; ++r) {
       const int j = lane * SPL + r;
       const float lam = (float)j * up.scale;                    // interpolation weight towards frame f + 1 (core.py:66-70)
       const float gv = gp[r];
-      s_theta[j] = kTwoPiF * cfg.wrap(base + pre[r], ip);
+      s_theta[j] = kTwoPiF * xs[r];
       s_gw[0][j] = gv * (1.0f - lam);
       s_gw[1][j] = gv * lam;
     }

@@ -20,6 +20,26 @@ __device__ __forceinline__ void frame_phase(const float* __restrict__ f0_row, in
   double pre[SPL];
   double acc = 0.0;
   const Upsampler::Row3 rows = up.load3(f0_row, f);
+  if (POW2 && cfg.infer) {                            // wave-uniform: sum double(f0u) first, scale once (PhaseCfg)
+#pragma unroll
+    for (int r = 0; r < SPL; ++r) {
+      int j = lane * SPL + r;
+      float v = 0.f;
+      if (j < hop) {
+        v = up.at3_pow2(rows, j);
+        acc += (double)v;
+      }
+      o.f0u[r] = v;
+      pre[r] = acc;
+    }
+    const double base = cfg.with_ip(cfg.scaled(wave_excl_scan(acc, lane), phase0), ip);
+#pragma unroll
+    for (int r = 0; r < SPL; ++r) o.x[r] = cfg.wrap_cycles(cfg.scaled(pre[r], base));
+    return;
+  }
+  // infer == 0, and the general interpolation (hop not a power of two, or above 512: the launchers' POW2 = false), which keeps the
+  // per-sample quotients: with a loop per form the compiler hoists its SPL long interpolations above the branch, and the
+  // SPL = 16 and 32 kernels lose an occupancy step
 #pragma unroll
   for (int r = 0; r < SPL; ++r) {
     int j = lane * SPL + r;

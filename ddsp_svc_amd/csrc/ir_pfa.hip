@@ -494,28 +494,34 @@ __device__ __forceinline__ void taps_pfa510_body(const TapsJobs& jobs, const Exc
     const int t = !act ? 0 : (sym ? tid >> 4 : tid / 30), n2 = !act ? 0 : (sym ? tid & 15 : tid - 30 * t);
     f32x2 z[17];
     {
-      const float* ra = re_s + (2 * t) * NB;
-      const float* rb = ra + NB;
-      const float* ia = im_s + (2 * t) * NB;
-      const float* ib = ia + NB;
-      int k = 17 * n2;                                     // < 510
+      // The gather map in closed form (EXPERIMENTS 6.19, part 2).  Point n1 reads bin k = (17 n2 + 30 n1) mod N folded to
+      // kk = min(k, N - k).  With c the signed residue of 30 n1 (a constant per unrolled point) the sum x = 17 n2 + c lies in
+      // (-N/2, N/2 + 493], and over [-N/2, 3 N/2] the fold is the triangle wave kk = | |x - N/2| - N/2 |: two absolute
+      // differences, in BYTES and with the row's offset as the second one's addend, so they are the address (as stage B's store).
+      const char* const Ub = reinterpret_cast<const char*>(re_s);
+      const unsigned row_b = 4u * (unsigned)(2 * t * NB);  // rows 2t (a) and 2t + 1 (b)
+      const unsigned a4 = 68u * (unsigned)n2;              // 4 * 17 n2
+      constexpr unsigned IM = 4u * ROWS * NB;              // im_s - re_s, bytes
       if (KIND == KIND_REAL) {
 #pragma unroll
         for (int n1 = 0; n1 < 17; ++n1) {
-          const int kk = k > HALF ? NT - k : k;
-          z[n1] = f32x2{ra[kk], rb[kk]};
-          k += 30;
-          if (k >= NT) k -= NT;
+          const int c = signed_residue(30 * n1);
+          const unsigned at = sad(sad(a4, 4u * (unsigned)(HALF - c)), 4u * HALF, row_b);
+          z[n1] = f32x2{*reinterpret_cast<const float*>(Ub + at), *reinterpret_cast<const float*>(Ub + at + 4u * NB)};
         }
       } else {
+        // the mirrored half (k > N/2: the conjugate bin) is x in (-N/2, 0) or (N/2, N): for c < 0 the sum stays below N, for
+        // c >= 0 it does not go below 0, so either way ONE unsigned comparison of x decides
 #pragma unroll
         for (int n1 = 0; n1 < 17; ++n1) {
-          const bool mir = k > HALF;
-          const int kk = mir ? NT - k : k;
+          const int c = signed_residue(30 * n1);
+          const unsigned at = sad(sad(a4, 4u * (unsigned)(HALF - c)), 4u * HALF, row_b);
+          const unsigned x4 = a4 + (unsigned)(4 * c);      // 4 x, two's complement
+          const bool mir = c < 0 ? x4 > 4u * HALF : x4 - 4u * (HALF + 1) < 4u * (HALF - 1);
           const float sg = mir ? -1.0f : 1.0f;
-          z[n1] = f32x2{fmaf(-sg, ib[kk], ra[kk]), fmaf(sg, ia[kk], rb[kk])};
-          k += 30;
-          if (k >= NT) k -= NT;
+          const float ra = *reinterpret_cast<const float*>(Ub + at), rb = *reinterpret_cast<const float*>(Ub + at + 4u * NB);
+          const float ia = *reinterpret_cast<const float*>(Ub + at + IM), ib = *reinterpret_cast<const float*>(Ub + at + IM + 4u * NB);
+          z[n1] = f32x2{fmaf(-sg, ib, ra), fmaf(sg, ia, rb)};
         }
       }
     }

@@ -5,8 +5,16 @@
 // utterance.  It is done as a three-level scan: each lane adds its own consecutive samples, a
 // wave64 butterfly adds the 64 lanes of one frame (k_phase_frame_sums), and one small workgroup
 // per utterance scans the frame totals (k_phase_frame_scan).  Consumers rebuild x[t] from the
-// per-frame start value with one more wave scan (frame_phase() below) instead of reading a
+// per-frame start value with one more wave scan (frame_phase(), frame_phase.h) instead of reading a
 // [B,T] tensor back from HBM.
+//
+// Under infer, in the shift form of the interpolation (hop a power of two up to 512: every shipped model), nothing divides per
+// sample: lanes and waves add double(f0u) -- float32 values, an exact float64 sum unless magnitudes 2^29 apart meet in one
+// frame -- and the SUM is scaled by RN(1 / sr) once: a frame's total is wave_sum(S) * rsr_d, a sample's phase
+// fma(S_r, rsr_d, base) (PhaseCfg, ddsp_common.h).  Against the sum of the correctly rounded quotients that moves a frame's
+// phase by ~1e-15 cycles; a float32 x resolves 3e-8, and a handful of x per million move by one float32 ulp
+// (tests/test_phase_sum_first.py counts them).  infer == 0 (float32 quotients) and the general interpolation are bit for bit
+// what they were.
 #include "ddsp_common.h"
 #include "kernels.h"
 
@@ -52,6 +60,29 @@ __global__ void __launch_bounds__(256) k_remove_above_fmax(const float* __restri
 #endif
 constexpr int PH_FRAMES_PER_WAVE = DDSP_PH_FPW;      // consecutive frames a wave walks: amortises the launch of tiny workgroups
 
+// the total of one frame by one wave (wave-uniform result).  infer, in the shift form of the interpolation: the float64 sum of
+// the upsampled float32 values, scaled once; otherwise the sum of the per-sample quotients
+template <int SPL, bool POW2>
+__device__ __forceinline__ double frame_total(const Upsampler::Row3 rows, int hop, const Upsampler& up, const PhaseCfg& cfg,
+                                              int lane) {
+  double acc = 0.0;
+  if (POW2 && cfg.infer) {                          // wave-uniform, outside the unrolled loop
+#pragma unroll
+    for (int r = 0; r < SPL; ++r) {
+      int j = lane * SPL + r;
+      if (j < hop) acc += (double)up.at3_pow2(rows, j);
+    }
+    return wave_sum(acc) * cfg.rsr_d;
+  }
+  // the general interpolation (hop not a power of two, or above 512) keeps the per-sample quotients: frame_phase(), frame_phase.h
+#pragma unroll
+  for (int r = 0; r < SPL; ++r) {
+    int j = lane * SPL + r;
+    if (j < hop) acc += cfg.term(POW2 ? up.at3_pow2(rows, j) : up.at3_in_frame(rows, j, hop));
+  }
+  return wave_sum(acc);
+}
+
 template <int SPL, bool POW2>
 __global__ void __launch_bounds__(256) k_phase_frame_sums(const float* __restrict__ f0_frames, long n_frames, int F,
                                                           int hop, Upsampler up, PhaseCfg cfg,
@@ -68,14 +99,7 @@ __global__ void __launch_bounds__(256) k_phase_frame_sums(const float* __restric
     if (fr >= n_frames) return;                     // wave-uniform
     if (f == F) { f = 0; ++b; }
     const float* row = f0_frames + (long)b * F;
-    const Upsampler::Row3 rows = up.load3(row, f);
-    double acc = 0.0;
-#pragma unroll
-    for (int r = 0; r < SPL; ++r) {
-      int j = lane * SPL + r;
-      if (j < hop) acc += cfg.term(POW2 ? up.at3_pow2(rows, j) : up.at3_in_frame(rows, j, hop));
-    }
-    acc = wave_sum(acc);
+    const double acc = frame_total<SPL, POW2>(up.load3(row, f), hop, up, cfg, lane);
     if (lane == 0) sums[fr] = acc;
   }
 }
@@ -97,7 +121,9 @@ __device__ __forceinline__ void phase_scan_utterance(const float* __restrict__ f
   for (int f = lo; f < hi; ++f) local += s[f];
   part[tid] = local;
   __syncthreads();
-  // Hillis-Steele inclusive scan over the 256 partials
+  // Hillis-Steele inclusive scan over the 256 partials.  (One float64 DPP scan per wave and a carry over four wave totals in LDS,
+  // two barriers instead of seventeen, was built and changed nothing: 4.97 -> 4.99 us, EXPERIMENTS 6.20 -- the launch is B workgroups
+  // on an otherwise idle chip, and its length is the launch and the serial walk of the chunks' global loads and stores.)
   for (int d = 1; d < 256; d <<= 1) {
     double u = (tid >= d) ? part[tid - d] : 0.0;
     __syncthreads();
@@ -143,14 +169,7 @@ __global__ void __launch_bounds__(1024) k_phase_small(const float* __restrict__ 
   const float* row = f0_frames + b * F;
 #pragma unroll 1
   for (int f = wave; f < F; f += 16) {
-    const Upsampler::Row3 rows = up.load3(row, f);
-    double acc = 0.0;
-#pragma unroll
-    for (int r = 0; r < SPL; ++r) {
-      const int j = lane * SPL + r;
-      if (j < hop) acc += cfg.term(up.at3_pow2(rows, j));
-    }
-    acc = wave_sum(acc);
+    const double acc = frame_total<SPL, true>(up.load3(row, f), hop, up, cfg, lane);
     if (lane == 0) { tot[f] = acc; sums[b * F + f] = acc; }
   }
   __syncthreads();
@@ -176,6 +195,21 @@ __global__ void __launch_bounds__(256) k_phase_expand(const float* __restrict__ 
   double pre[SPL];
   double acc = 0.0;
   const Upsampler::Row3 rows = up.load3(row, f);
+  if (SPL == 8 && up.shift > 0 && cfg.infer) {      // wave-uniform: as frame_phase<8, true>() (frame_phase.h)
+#pragma unroll
+    for (int r = 0; r < SPL; ++r) {
+      int j = lane * SPL + r;
+      if (j < hop) acc += (double)up.at3_in_frame(rows, j, hop);
+      pre[r] = acc;
+    }
+    const double base = cfg.with_ip(cfg.scaled(wave_excl_scan(acc, lane), phase0[fr]), ip);
+#pragma unroll
+    for (int r = 0; r < SPL; ++r) {
+      int j = lane * SPL + r;
+      if (j < hop) x[(b * F + f) * (long)hop + j] = cfg.wrap_cycles(cfg.scaled(pre[r], base));
+    }
+    return;
+  }
 #pragma unroll
   for (int r = 0; r < SPL; ++r) {
     int j = lane * SPL + r;
