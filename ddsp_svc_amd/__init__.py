@@ -7,7 +7,7 @@ Sins/CombSub forward pass of yxlllc/DDSP-SVC).
   mel       -- nsf_hifigan.nvSTFT.STFT.get_mel (the cascade's waveform -> log-mel front-end)
   nsf_source -- nsf_hifigan.models.SourceModuleHnNSF (SineGen + merge), the vocoder's harmonic source
   nsf_generator -- nsf_hifigan.models.ResBlock1 and the per-stage block sum of Generator.forward: fused f32 MFMA conv pairs
-  conformer -- the control network's ConformerConvModule / conv-only CFNEncoderLayer: one fused f32 MFMA launch per module
+  conformer -- the control network's ConformerConvModule / conv-only CFNEncoderLayer: one fused f32 MFMA launch per module, three in its channel-split form for real-time sizes (the conv-only ConformerNaiveEncoder)
   attention -- PCmer's performer attention (FastAttention / SelfAttention): two fused f32 MFMA launches per call
   wavenet   -- the diffusion denoiser's WaveNet ResidualBlock: one fused f32 MFMA launch per layer, the skip sum in place; two launches in its channel-split form for real-time sizes
   naive_v2  -- the reflow / diffusion-fast denoiser's NaiveV2DiffLayer: two fused f32 MFMA launches per layer, four in its channel-split form for real-time sizes

@@ -122,6 +122,9 @@ SIGNATURES = {
     "ddsp_hip_conformer_conv_pack_bytes": (c_size_t, [c_int, c_int]),
     "ddsp_hip_conformer_conv_pack": (c_int, [P, P, P, P, P, P, P, P, c_int, P, c_size_t]),
     "ddsp_hip_conformer_conv": (c_int, [P, P, P, c_size_t, c_int, c_long, c_int, c_int, c_float, c_int, P]),
+    "ddsp_hip_conformer_conv_split_tile": (c_int, [c_int]),
+    "ddsp_hip_conformer_conv_split_workspace_bytes": (c_size_t, [c_long, c_long, c_int]),
+    "ddsp_hip_conformer_conv_split": (c_int, [P, P, P, c_size_t, P, c_size_t, c_int, c_long, c_int, c_int, c_float, c_int, P]),
     "ddsp_hip_wavenet_layer_tile": (c_int, [c_int, c_int]),
     "ddsp_hip_wavenet_layer_pack_bytes": (c_size_t, [c_int, c_int]),
     "ddsp_hip_wavenet_layer_pack": (c_int, [P, P, P, P, P, P, c_int, c_int, P, c_size_t]),

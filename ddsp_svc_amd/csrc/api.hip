@@ -9,6 +9,7 @@
 #include "resblock.h"
 #include "generator_tail.h"
 #include "conformer_conv.h"
+#include "conformer_split.h"
 #include "wavenet_layer.h"
 #include "wavenet_split.h"
 #include "performer_attention.h"
@@ -1536,6 +1537,27 @@ int ddsp_hip_conformer_conv(const float* x, float* y, const void* packed, size_t
   return finish();
 }
 
+int ddsp_hip_conformer_conv_split_tile(int D) { return cconv::shape_ok(D) ? ccs::kT : 0; }
+
+size_t ddsp_hip_conformer_conv_split_workspace_bytes(long B, long L, int D) {
+  if (B < 0 || L < 1 || L > (1L << 40) || !cconv::shape_ok(D) || !ccs::in_range(B, L)) return 0;
+  return conformer_split_ws_bytes(B, L, D);
+}
+
+int ddsp_hip_conformer_conv_split(const float* x, float* y, const void* packed, size_t packed_bytes, void* ws, size_t ws_bytes, int B,
+                                  long L, int D, int norm, float eps, int add_input, void* stream) {
+  if (B < 0 || L < 1 || !(eps == eps) || eps - eps != 0.f) return DDSP_HIP_EINVAL;
+  if (!cconv::shape_ok(D) || L > (1L << 40) || !ccs::in_range(B, L)) return DDSP_HIP_ESHAPE;
+  if (B == 0) return 0;
+  if (!x || !y || !packed || !ws || x == y) return DDSP_HIP_EINVAL;
+  if (packed_bytes < conformer_conv_pack_bytes(D, norm) || ws_bytes < conformer_split_ws_bytes(B, L, D)) return DDSP_HIP_EWS;
+  if ((reinterpret_cast<uintptr_t>(packed) & 3) || (reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(y) & 15) ||
+      (reinterpret_cast<uintptr_t>(ws) & 3))
+    return DDSP_HIP_EINVAL;                            // the kernels read x and write y 4 channels at a time
+  launch_conformer_split(x, y, static_cast<const float*>(packed), static_cast<float*>(ws), B, L, D, norm ? 1 : 0, eps,
+                         add_input ? 1 : 0, S(stream));
+  return finish();
+}
 
 int ddsp_hip_wavenet_layer_tile(int C, int H) { return wnet::shape_ok(C, H) ? wnet::kTile : 0; }
 

@@ -64,7 +64,31 @@ struct Args {
   int norm, add_input;
 };
 
+// sigmoid and layer_norm_row are shared with the channel-split form (conformer_split.h): both kernels compile one text
 __device__ __forceinline__ float sigmoid(float v) { return 1.f / (1.f + expf(-v)); }   // expf(-v) = inf gives 0, never a NaN
+
+// LayerNorm of one frame's D channels in place, by one wave: sums and the normalisation in double (a frame of mean 1e3 does not
+// cancel), lane l adds channels l + 64 i in the order of i, then an xor-shuffle reduction
+template <int D>
+__device__ __forceinline__ void layer_norm_row(float* row, const float* gamma, const float* beta, float eps, int lane) {
+  double s = 0.0;
+#pragma unroll
+  for (int i = 0; i < D / 64; ++i) s += (double)row[lane + 64 * i];
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m);
+  const double mean = s / D;
+  double q = 0.0;
+#pragma unroll
+  for (int i = 0; i < D / 64; ++i) { const double e = (double)row[lane + 64 * i] - mean; q += e * e; }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) q += __shfl_xor(q, m);
+  const double rstd = 1.0 / sqrt(q / D + (double)eps);
+#pragma unroll
+  for (int i = 0; i < D / 64; ++i) {
+    const int k = lane + 64 * i;
+    row[k] = (float)(((double)row[k] - mean) * rstd * (double)gamma[k] + (double)beta[k]);
+  }
+}
 
 template <int D>
 __global__ __launch_bounds__(kThreads) void k_conformer_conv(Args a) {
@@ -95,26 +119,7 @@ __global__ __launch_bounds__(kThreads) void k_conformer_conv(Args a) {
   if (a.norm) {
     const float* gamma = tab + off_gamma(D);
     const float* beta = gamma + D;
-    for (int c = wave; c < kNW; c += kWaves) {
-      float* row = xs + c * XS;
-      double s = 0.0;
-#pragma unroll
-      for (int i = 0; i < D / 64; ++i) s += (double)row[lane + 64 * i];
-#pragma unroll
-      for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m);
-      const double mean = s / D;
-      double q = 0.0;
-#pragma unroll
-      for (int i = 0; i < D / 64; ++i) { const double e = (double)row[lane + 64 * i] - mean; q += e * e; }
-#pragma unroll
-      for (int m = 32; m >= 1; m >>= 1) q += __shfl_xor(q, m);
-      const double rstd = 1.0 / sqrt(q / D + (double)a.eps);
-#pragma unroll
-      for (int i = 0; i < D / 64; ++i) {
-        const int k = lane + 64 * i;
-        row[k] = (float)(((double)row[k] - mean) * rstd * (double)gamma[k] + (double)beta[k]);
-      }
-    }
+    for (int c = wave; c < kNW; c += kWaves) layer_norm_row<D>(xs + c * XS, gamma, beta, a.eps, lane);
     __syncthreads();
   }
 

@@ -603,6 +603,21 @@ int ddsp_hip_conformer_conv_pack(const float* w1, const float* b1, const float* 
 int ddsp_hip_conformer_conv(const float* x, float* y, const void* packed, size_t packed_bytes, int B, long L, int D, int norm,
                             float eps, int add_input, void* stream);
 
+/* The same module in its channel-split form, csrc/conformer_split.h, for calls of a few hundred frames: a frame tile of 16, the
+ * channels split over workgroups and waves, three plain launches on the stream (the LayerNorm, first GEMM and GLU; the stencil and
+ * SiLU; the output GEMM and residual), every sum in the order of ddsp_hip_conformer_conv and the LayerNorm and sigmoid its own
+ * code, so the two give the same bits.  It reads the table of ddsp_hip_conformer_conv_pack.  As above, these entry points came
+ * after version 165 without a version step.
+ * ddsp_hip_conformer_conv_split_tile: frames per workgroup (16); 0 for a D the kernels do not take.
+ * ddsp_hip_conformer_conv_split_workspace_bytes: 4 B L D floats (g and h [B, 2 D, L]); 0 for arguments the call below refuses.
+ * ddsp_hip_conformer_conv_split: the arguments, checks and error codes of ddsp_hip_conformer_conv, a workspace (null or
+ * misaligned: DDSP_HIP_EINVAL, short: DDSP_HIP_EWS) and B ceil(L / 16) <= 4096 (DDSP_HIP_ESHAPE beyond: the tiled form is for the
+ * rest).  16.5 KB of LDS in the first launch.  No allocation, no synchronisation. */
+int ddsp_hip_conformer_conv_split_tile(int D);
+size_t ddsp_hip_conformer_conv_split_workspace_bytes(long B, long L, int D);
+int ddsp_hip_conformer_conv_split(const float* x, float* y, const void* packed, size_t packed_bytes, void* ws, size_t ws_bytes, int B,
+                                  long L, int D, int norm, float eps, int add_input, void* stream);
+
 /* The residual layer of the diffusion denoiser's WaveNet (diffusion/wavenet.py:31-61, ResidualBlock with dilation 1),
  * csrc/wavenet_layer.h.  As above, these entry points came after version 165 without a version step.
  *   z = Conv1d(C, 2 C, 3, padding 1)(x + d) + Conv1d(H, 2 C, 1)(cond);  g = sigmoid(z[:C]) tanh(z[C:]);  o = Conv1d(C, 2 C, 1)(g)
