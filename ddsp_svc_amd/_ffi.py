@@ -112,6 +112,11 @@ SIGNATURES = {
     "ddsp_hip_resblock1_pack": (c_int, [P, P, c_int, c_int, c_int, P, c_size_t]),
     "ddsp_hip_resblock1_workspace_bytes": (c_size_t, [c_int, c_int, c_long, c_int]),
     "ddsp_hip_resblock1": (c_int, [P, P, P, c_size_t, c_int, c_int, c_long, c_int, P, c_int, P, c_float, P, c_size_t, P]),
+    "ddsp_hip_resblock1_wide_tile": (c_int, [c_int, c_int]),
+    "ddsp_hip_resblock1_wide_pack_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "ddsp_hip_resblock1_wide_pack": (c_int, [P, P, c_int, c_int, c_int, P, c_size_t]),
+    "ddsp_hip_resblock1_wide_workspace_bytes": (c_size_t, [c_int, c_int, c_long, c_int]),
+    "ddsp_hip_resblock1_wide": (c_int, [P, P, P, c_size_t, c_int, c_int, c_long, c_int, P, c_int, P, c_float, P, c_size_t, P]),
     "ddsp_hip_upsample_stage_tile": (c_int, [c_int, c_int]),
     "ddsp_hip_upsample_stage_pack_bytes": (c_size_t, [c_int, c_int, c_int]),
     "ddsp_hip_upsample_stage_pack": (c_int, [P, P, P, P, c_int, c_int, c_int, P, c_size_t]),

@@ -7,6 +7,7 @@
 #include "resample.h"
 #include "frame_features.h"
 #include "resblock.h"
+#include "resblock_wide.h"
 #include "generator_tail.h"
 #include "conformer_conv.h"
 #include "conformer_split.h"
@@ -1468,6 +1469,43 @@ int ddsp_hip_resblock1(const float* x, float* y, const void* packed, size_t pack
   if ((reinterpret_cast<uintptr_t>(packed) & 3) || (reinterpret_cast<uintptr_t>(ws) & 3)) return DDSP_HIP_EINVAL;
   launch_resblock1(x, y, static_cast<const float*>(packed), B, C, T, k, dilations, pairs, acc_in, scale, static_cast<float*>(ws),
                    S(stream));
+  return finish();
+}
+
+int ddsp_hip_resblock1_wide_tile(int C, int k) { return resblock_wide::shape_ok(C, k) ? resblock_wide::kTile : 0; }
+
+size_t ddsp_hip_resblock1_wide_pack_bytes(int C, int k, int pairs) { return resblock_wide_pack_bytes(C, k, pairs); }
+
+int ddsp_hip_resblock1_wide_pack(const float* w, const float* b, int C, int k, int pairs, void* packed, size_t packed_bytes) {
+  if (!w || !b || !packed || pairs < 1) return DDSP_HIP_EINVAL;
+  const size_t need = resblock_wide_pack_bytes(C, k, pairs);
+  if (need == 0) return DDSP_HIP_ESHAPE;
+  if (packed_bytes < need) return DDSP_HIP_EWS;
+  resblock_wide_pack(w, b, C, k, pairs, static_cast<float*>(packed));
+  return 0;
+}
+
+size_t ddsp_hip_resblock1_wide_workspace_bytes(int B, int C, long T, int pairs) {
+  if (B < 0 || T < 1 || pairs < 1 || pairs > resblock_wide::kMaxPairs || (C != 128 && C != 256) || T > (1L << 40)) return 0;
+  return resblock_wide_ws_bytes(B, C, T, pairs);
+}
+
+int ddsp_hip_resblock1_wide(const float* x, float* y, const void* packed, size_t packed_bytes, int B, int C, long T, int k,
+                            const int* dilations, int pairs, const float* acc_in, float scale, void* ws, size_t ws_bytes,
+                            void* stream) {
+  if (B < 0 || T < 1 || pairs < 1 || !dilations || !(scale == scale)) return DDSP_HIP_EINVAL;
+  if (!resblock_wide::shape_ok(C, k) || pairs > resblock_wide::kMaxPairs || T > (1L << 40)) return DDSP_HIP_ESHAPE;
+  for (int p = 0; p < pairs; ++p) {
+    if (dilations[p] < 1) return DDSP_HIP_EINVAL;
+    if (!resblock_wide::dilation_ok(k, dilations[p])) return DDSP_HIP_ESHAPE;    // a chunk's image would not fit in LDS
+  }
+  if (B == 0) return 0;
+  if (!x || !y || !packed || x == y || acc_in == x) return DDSP_HIP_EINVAL;
+  if (packed_bytes < resblock_wide_pack_bytes(C, k, pairs)) return DDSP_HIP_EWS;
+  if (!ws || ws_bytes < resblock_wide_ws_bytes(B, C, T, pairs)) return DDSP_HIP_EWS;
+  if ((reinterpret_cast<uintptr_t>(packed) & 3) || (reinterpret_cast<uintptr_t>(ws) & 3)) return DDSP_HIP_EINVAL;
+  launch_resblock1_wide(x, y, static_cast<const float*>(packed), B, C, T, k, dilations, pairs, acc_in, scale,
+                        static_cast<float*>(ws), S(stream));
   return finish();
 }
 

@@ -16,6 +16,9 @@ Dispatch (``hip_eligible``): a float32 tensor on the GPU, no gradient needed, au
 kernel's LDS image holds, and plain ``Conv1d`` weights -- every conv of the block has had ``remove_weight_norm`` applied (the
 weight-norm hook recomputes ``weight`` in a forward pre-hook, which a call that bypasses ``Conv1d.forward`` would never run).
 Everything else -- 128 / 256 channels, ``ResBlock2``, training, CPU tensors -- takes the reference's own forward unchanged.
+The 128- and 256-channel blocks have a kernel too, the wide form (csrc/resblock_wide.h: one convolution per launch, the input
+channels in chunks of 64): ``resblock1`` and ``mrf_stage`` always take them, the hooks only while ``ROUTE_WIDE`` is set
+(``patch_reference_generator(wide=True)``, or the flag itself for a stand-in), under the same conditions otherwise.
 ``TORCH_FASTER`` lists the (C, k) the measurements on one MI355X (tools/resblock_bench.py) found faster as the
 torch op chain: those are routed to it as well.
 
@@ -37,10 +40,14 @@ from ._modules import (autocast_on, clear_packed, drop_workspaces, needs_grad, o
 from ._patching import park, run_reference, unpark
 
 CHANNELS = (16, 32, 64)
+WIDE_CHANNELS = (128, 256)                             # the wide form (csrc/resblock_wide.h): one convolution per launch
+ROUTE_WIDE = False                                     # the hooks send 128- / 256-channel blocks to it: patch_reference_generator(wide=True)
 KERNEL_SIZES = (3, 7, 11)
 LRELU_SLOPE = 0.1
 # (C, k) -> the number of columns T below which the same-GPU torch chain was measured faster (None: at every T)
-TORCH_FASTER = {}
+# The wide form's entries are profiles/resblock_wide_{latency,throughput}.json's ``torch_faster`` lists (one MI355X, B = 1 x 203
+# frames and B = 32 x 861 frames): torch won at both sizes everywhere but at (128, 3), where the kernel won at T = 64 x 861.
+TORCH_FASTER = {(256, 3): None, (256, 7): None, (256, 11): None, (128, 3): 64 * 861, (128, 7): None, (128, 11): None}
 UPSAMPLE_RATES = (2, 4, 8)
 NOISE_STRIDES = (1, 2, 4)
 HEAD_SLOPE = 0.01                                      # F.leaky_relu's default, models.py:260
@@ -60,6 +67,11 @@ def tile(C, k):
     return int(_ffi.lib().ddsp_hip_resblock1_tile(C, k))
 
 
+def wide_tile(C, k):
+    """output columns per workgroup of the wide form (``ddsp_hip_resblock1_wide_tile``): 128 for every k"""
+    return int(_ffi.lib().ddsp_hip_resblock1_wide_tile(C, k))
+
+
 def _flat(weights):
     return [t for pair in weights for t in pair]
 
@@ -67,14 +79,16 @@ def _flat(weights):
 def _pack(dims, flat):
     """the host table of one block's ``(w1, b1, w2, b2)`` per pair, for ``packed_table``"""
     (C, k), pairs, lib = dims, len(flat) // 4, _ffi.lib()
-    nbytes = int(lib.ddsp_hip_resblock1_pack_bytes(C, k, pairs))
+    wide = C in WIDE_CHANNELS
+    nbytes = int((lib.ddsp_hip_resblock1_wide_pack_bytes if wide else lib.ddsp_hip_resblock1_pack_bytes)(C, k, pairs))
     if nbytes == 0:
         raise ValueError("resblock1: C = %d, k = %d, %d pairs is outside the kernel's range" % (C, k, pairs))
     with torch.no_grad():
         w = torch.stack([t.detach().to("cpu", torch.float32) for t in flat[0::2]]).contiguous()
         b = torch.stack([t.detach().to("cpu", torch.float32) for t in flat[1::2]]).contiguous()
     host = torch.empty(nbytes // 4, dtype=torch.float32)
-    _ffi.check(lib.ddsp_hip_resblock1_pack(w.data_ptr(), b.data_ptr(), C, k, pairs, host.data_ptr(), nbytes))
+    entry = lib.ddsp_hip_resblock1_wide_pack if wide else lib.ddsp_hip_resblock1_pack
+    _ffi.check(entry(w.data_ptr(), b.data_ptr(), C, k, pairs, host.data_ptr(), nbytes))
     return host
 
 
@@ -96,17 +110,27 @@ def shape_ok(C, k, dilations):
     return all(int(d) >= 1 and C * ((112 + (k - 1) * int(d) + 31) // 32 * 32 + 16) <= 16384 for d in dilations)
 
 
+def wide_shape_ok(C, k, dilations):
+    """what the wide form takes: C in {128, 256}, and a 64-channel chunk of the x image, 64 rows of 128 + (k - 1) d columns
+    padded to 16 mod 32, within 64 KB -- d <= 11 at k = 11, 18 at 7, 56 at 3"""
+    if C not in WIDE_CHANNELS or k not in KERNEL_SIZES or not 1 <= len(dilations) <= 8:
+        return False
+    return all(int(d) >= 1 and 64 * ((112 + (k - 1) * int(d) + 31) // 32 * 32 + 16) <= 16384 for d in dilations)
+
+
 def resblock1(x, weights, dilations, acc=None, scale=None, out=None):
     """``ResBlock1.forward`` on the HIP kernel: ``x [B, C, T]`` float32, ``weights`` one ``(w1 [C, C, k], b1 [C], w2, b2)`` per
     pair, ``dilations`` conv 1's dilation per pair.  Returns ``(acc + block(x)) / scale``: ``acc`` (optional, same shape) may
     be ``out``; ``scale`` None means no division.  No synchronisation; the only allocation is the result (when ``out`` is
-    None) once the weight table and the hand-over buffer of this shape exist."""
+    None) once the weight table and the hand-over buffer of this shape exist.  C in {16, 32, 64} runs the fused pair kernel
+    (csrc/resblock.h), C in {128, 256} the wide form (csrc/resblock_wide.h); whatever ``ROUTE_WIDE`` says: that is the hooks'."""
     _ffi.check_device(x, acc, out)
     if x.dtype != torch.float32 or x.dim() != 3:
         raise ValueError("resblock1: x must be a float32 [B, C, T] tensor")
     B, C, T = x.shape
     k = weights[0][0].shape[-1]
-    if len(weights) != len(dilations) or not shape_ok(C, k, dilations):
+    wide = C in WIDE_CHANNELS
+    if len(weights) != len(dilations) or not (wide_shape_ok if wide else shape_ok)(C, k, dilations):
         raise ValueError("resblock1: C = %d, k = %d, dilations %s is outside the kernel's range" % (C, k, tuple(dilations)))
     for w1, b1, w2, b2 in weights:
         if tuple(w1.shape) != (C, C, k) or tuple(w2.shape) != (C, C, k) or tuple(b1.shape) != (C,) or tuple(b2.shape) != (C,):
@@ -122,15 +146,16 @@ def resblock1(x, weights, dilations, acc=None, scale=None, out=None):
     if B == 0:
         return y
     lib = _ffi.lib()
-    table = packed_table("resblock", (C, k), _flat(weights), x.device, _pack)
+    table = packed_table("resblock_wide" if wide else "resblock", (C, k), _flat(weights), x.device, _pack)
     pairs = len(dilations)
-    nws = int(lib.ddsp_hip_resblock1_workspace_bytes(B, C, T, pairs))
+    nws = int((lib.ddsp_hip_resblock1_wide_workspace_bytes if wide else lib.ddsp_hip_resblock1_workspace_bytes)(B, C, T, pairs))
     ws = _workspace(nws, x) if nws else None          # its real size goes to the library, which refuses one too small
     dil = (ctypes.c_int * pairs)(*[int(d) for d in dilations])
     CALLS["hip"] += 1
-    _ffi.check(lib.ddsp_hip_resblock1(x.data_ptr(), y.data_ptr(), table.data_ptr(), table.numel() * 4, B, C, T, k,
-                                      ctypes.addressof(dil), pairs, _ffi.ptr(acc), 0.0 if scale is None else float(scale),
-                                      _ffi.ptr(ws), 0 if ws is None else ws.numel() * 4, _ffi.stream_of(x)))
+    entry = lib.ddsp_hip_resblock1_wide if wide else lib.ddsp_hip_resblock1
+    _ffi.check(entry(x.data_ptr(), y.data_ptr(), table.data_ptr(), table.numel() * 4, B, C, T, k, ctypes.addressof(dil), pairs,
+                     _ffi.ptr(acc), 0.0 if scale is None else float(scale), _ffi.ptr(ws), 0 if ws is None else ws.numel() * 4,
+                     _ffi.stream_of(x)))
     return y
 
 
@@ -253,7 +278,7 @@ def _block_spec(block):
         return None
     C, k = c0.in_channels, c0.kernel_size[0]
     dil = [c.dilation[0] if isinstance(c, torch.nn.Conv1d) else 0 for c in c1s]
-    if not shape_ok(C, k, dil):
+    if not shape_ok(C, k, dil) and not (ROUTE_WIDE and wide_shape_ok(C, k, dil)):
         return None
     if not all(_plain_conv(a, C, k, d) and _plain_conv(b, C, k, 1) for a, b, d in zip(c1s, c2s, dil)):
         return None
@@ -408,10 +433,14 @@ def generator_forward(gen, x, f0, fallback=None):
     return head_forward(gen.conv_post, x)
 
 
-def patch_reference_generator():
+def patch_reference_generator(wide=False):
     """Route ``nsf_hifigan.models.ResBlock1.forward`` and, in ``Generator.forward`` of an importable reference checkout, each
-    stage's upsampling seam, its block sum and the output head through the dispatchers above.  Idempotent; returns the module."""
+    stage's upsampling seam, its block sum and the output head through the dispatchers above.  ``wide`` sets ``ROUTE_WIDE``: the
+    128- and 256-channel blocks go to the wide form as well, under the same conditions as the narrow ones.  Idempotent (the
+    last call's ``wide`` holds); returns the module."""
+    global ROUTE_WIDE
     import nsf_hifigan.models as nm
+    ROUTE_WIDE = bool(wide)
     ref_generator_forward = park(nm.Generator, "forward")
 
     def patched_forward(self, x, f0):
@@ -425,8 +454,10 @@ def patch_reference_generator():
 
 
 def unpatch_reference_generator():
-    """Undo ``patch_reference_generator()``."""
+    """Undo ``patch_reference_generator()``; ``ROUTE_WIDE`` is off afterwards."""
+    global ROUTE_WIDE
     import sys
+    ROUTE_WIDE = False
     nm = sys.modules.get("nsf_hifigan.models")
     if nm is not None:
         unpark(nm.ResBlock1, "forward")

@@ -13,7 +13,7 @@
  *   - tensors are float32 row-major; B = utterances, F = frames, hop = samples per frame,
  *     T = F*hop; control tensors take a row stride `ld` (floats between consecutive frames) so
  *     the torch.split views of Unit2Control's output can be passed without a copy;
- *   - more than 65 535 utterances in one call (a grid's limit in y and z): ddsp_hip_resblock1, ddsp_hip_upsample_stage,
+ *   - more than 65 535 utterances in one call (a grid's limit in y and z): ddsp_hip_resblock1(_wide), ddsp_hip_upsample_stage,
  *     ddsp_hip_output_head, ddsp_hip_conformer_conv, ddsp_hip_wavenet_layer, ddsp_hip_naive_v2_layer, ddsp_hip_resample and ddsp_hip_mel_shifted_spectrogram split the batch into launches of 65 535; ddsp_hip_fast_source and
  *     ddsp_hip_combsubsuperfast_synth run their exciter on a flat grid then; ddsp_hip_sine_source(_drawn),
  *     ddsp_hip_spectral_loss(_backward), ddsp_hip_stft_loss(_backward), ddsp_hip_mel_spectrogram_backward,
@@ -549,6 +549,27 @@ size_t ddsp_hip_resblock1_workspace_bytes(int B, int C, long T, int pairs);
 int ddsp_hip_resblock1(const float* x, float* y, const void* packed, size_t packed_bytes, int B, int C, long T, int k,
                        const int* dilations, int pairs, const float* acc_in, float scale, void* ws, size_t ws_bytes,
                        void* stream);
+
+/* The wide form of the above, csrc/resblock_wide.h: C in {128, 256}, k in {3, 7, 11} (DDSP_HIP_ESHAPE otherwise, C = 64 included:
+ * the entries above keep what they take and refuse).  Looked up by name like them; ddsp_hip_version() stays 165.  Same
+ * arguments, same result, same codes.  One convolution per launch, two launches per pair (per 65 535 utterances), f32 MFMA; the
+ * input channels pass through LDS in chunks of 64, each chunk one summation chain, the chunks' partial sums added in order.
+ *
+ * ddsp_hip_resblock1_wide_tile: output columns per workgroup, 128 for every k; 0 for a (C, k) this form does not take.
+ * ddsp_hip_resblock1_wide_pack_bytes / _pack: as ddsp_hip_resblock1_pack, same sizes (2 C C k + 2 C floats per pair), the
+ * fragments ordered per (64-row output slice, 64-channel chunk).  A table of one form is not the other's.
+ * ddsp_hip_resblock1_wide: dilations each >= 1 (DDSP_HIP_EINVAL) and small enough for a chunk's input to fit in 64 KB of LDS:
+ * 64 (16 + 32 ceil((112 + (k - 1) d) / 32)) <= 16384, i.e. d <= 11 at k = 11, 18 at k = 7, 56 at k = 3 (DDSP_HIP_ESHAPE).
+ * ws: ddsp_hip_resblock1_wide_workspace_bytes(B, C, T, pairs) bytes, never 0: the intermediate of a pair and the hand-over
+ * between pairs, min(pairs, 3) activations [B, C, T] (DDSP_HIP_EWS when short or null).  x must not be y or acc_in; acc_in
+ * may be y.  Row b of the result does not depend on B.  No allocation, no synchronisation. */
+int ddsp_hip_resblock1_wide_tile(int C, int k);
+size_t ddsp_hip_resblock1_wide_pack_bytes(int C, int k, int pairs);
+int ddsp_hip_resblock1_wide_pack(const float* w, const float* b, int C, int k, int pairs, void* packed, size_t packed_bytes);
+size_t ddsp_hip_resblock1_wide_workspace_bytes(int B, int C, long T, int pairs);
+int ddsp_hip_resblock1_wide(const float* x, float* y, const void* packed, size_t packed_bytes, int B, int C, long T, int k,
+                            const int* dilations, int pairs, const float* acc_in, float scale, void* ws, size_t ws_bytes,
+                            void* stream);
 
 /* The rest of the NSF-HiFiGAN generator between the 128-channel stage and the waveform (nsf_hifigan/models.py:249-252, :260-262),
  * csrc/generator_tail.h.  As above, these entry points came after version 165 without a version step.

@@ -8,6 +8,8 @@ same process, the two alternated rep by rep.
                       each block (C, k) on its own for the dispatcher's crossover table.  Call to result: a host clock around
                       the call and a device synchronise.
   --mode throughput   B = 32 x 10 s (F = 861): the same, device events around each call.
+  --stages wide       the two stages of the wide form (csrc/resblock_wide.h) instead: 256 channels at 8 F columns and 128 at
+                      64 F, in the same two modes (default: narrow, the three stages above)
 
 Every rep checks nothing; the first call of each pair is compared (max |hip - torch| relative to the output's RMS).  Prints
 one JSON document; --out writes it to a file as well.
@@ -26,7 +28,9 @@ import torch.nn.functional as F
 
 KS = (3, 7, 11)
 DIL = (1, 3, 5)
-STAGES = ((64, 128), (32, 256), (16, 512))             # (channels, columns per frame)
+STAGES = {"narrow": ((64, 128), (32, 256), (16, 512)),  # (channels, columns per frame)
+          "wide": ((256, 8), (128, 64))}
+PEAK_TFLOPS = 157.3                                     # f32 MFMA, MI355X
 
 
 def weights(C, k, dev, seed):
@@ -91,6 +95,7 @@ def compare(hip, ref, reps, warmup, events):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mode", choices=("latency", "throughput"), required=True)
+    ap.add_argument("--stages", choices=tuple(STAGES), default="narrow")
     ap.add_argument("--reps", type=int, default=0)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out")
@@ -103,22 +108,25 @@ def main():
     lat = args.mode == "latency"
     B, frames = (1, 203) if lat else (32, 861)
     reps = args.reps or (40 if lat else 6)
-    doc = {"mode": args.mode, "B": B, "frames": frames, "reps": reps, "timing": "host clock + synchronise" if lat else "device events",
+    wide = args.stages == "wide"
+    doc = {"mode": args.mode, "stage_set": args.stages, "B": B, "frames": frames, "reps": reps, "timing": "host clock + synchronise" if lat else "device events",
            "device": torch.cuda.get_device_name(0), "torch": torch.__version__, "stages": [], "blocks": []}
     with torch.no_grad():
-        for C, per_frame in STAGES:
+        for C, per_frame in STAGES[args.stages]:
             T = per_frame * frames
             x = torch.randn(B, C, T, generator=torch.Generator().manual_seed(C)).to(dev)
             blocks = [weights(C, k, dev, 10 * C + k) for k in KS]
             specs = [(ws, DIL) for ws in blocks]
             r = compare(lambda: NG.mrf_stage(x, specs), lambda: torch_stage(x, blocks), reps, args.warmup, not lat)
             flops = sum(2.0 * 2 * len(DIL) * C * C * k for k in KS) * B * T
-            r.update(C=C, T=T, launches_hip=3 * len(DIL), flops=flops, hip_tflops=flops / r["hip_ms"] * 1e-9)
+            r.update(C=C, T=T, launches_hip=(6 if wide else 3) * len(DIL), flops=flops, hip_tflops=flops / r["hip_ms"] * 1e-9,
+                     hip_share_of_f32_mfma_peak=flops / r["hip_ms"] * 1e-9 / PEAK_TFLOPS)
             doc["stages"].append(r)
             print("stage", json.dumps(r), flush=True)
             for k, ws in zip(KS, blocks):
                 rb = compare(lambda: NG.resblock1(x, ws, DIL), lambda: torch_block(x, ws), reps, args.warmup, not lat)
-                rb.update(C=C, k=k, T=T)
+                fb = 2.0 * 2 * len(DIL) * C * C * k * B * T
+                rb.update(C=C, k=k, T=T, hip_tflops=fb / rb["hip_ms"] * 1e-9, torch_tflops=fb / rb["torch_ms"] * 1e-9)
                 doc["blocks"].append(rb)
                 print("block", json.dumps(rb), flush=True)
             del x
