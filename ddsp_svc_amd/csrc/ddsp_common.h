@@ -313,4 +313,19 @@ __device__ __forceinline__ f32x2 sin_turns2(f32x2 a) {
   return f32x2{__builtin_amdgcn_sinf(r.x), __builtin_amdgcn_sinf(r.y)};
 }
 
+// (cos, sin) of fl32(pi32 * p): the phase factor of the spectral filters (stft.hip).  The reference forms
+// exp(mag + 1j * pi * phase) in complex64 (vocoder.py:661-664, :759-760), so its angle is the float32 product, which is off
+// the exact pi p by up to |p| pi 2^-24 radians -- and the parity bar is against the reference, not the mathematics: an exact
+// fract(p / 2) revolutions leaves it by 3.5e-5 relative RMS of the filtered signal at phases of sigma 300 (EXPERIMENTS.md).
+// Hence sin_turns' reduction of the rounded product, then the hardware cosine and sine, which take revolutions; same bound,
+// 3.9e-7 absolute for |pi p| <= 805 (tests/test_device_units.py).  4 VALU + 2 transcendental.
+__device__ __forceinline__ f32x2 cis_pi(float p) {
+  const float inv_hi = 0.15915494f, inv_lo = 6.4206383e-9f;      // as in sin_turns
+  const float a = kPiF * p;
+  const float n = rintf(a * inv_hi);
+  float r = fmaf(a, inv_hi, -n);
+  r = fmaf(a, inv_lo, r);
+  return f32x2{__builtin_amdgcn_cosf(r), __builtin_amdgcn_sinf(r)};
+}
+
 }  // namespace ddsp

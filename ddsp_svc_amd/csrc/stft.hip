@@ -3,7 +3,8 @@
 //
 // Both models frame the exciter and a noise draw with 50 % / 75 % overlap (frames of `win` samples every hop = 512,
 // win/2 samples of zero or reflect padding), window them, multiply the one-sided spectra by per-frame complex
-// filters exp(mag + i pi phase) predicted by Unit2Control, inverse-transform, window again and overlap-add
+// filters exp(mag + i fl32(pi32 phase)) predicted by Unit2Control (the angle is rounded to float32 as the reference's
+// complex64 exponential rounds it: cis_pi, ddsp_common.h), inverse-transform, window again and overlap-add
 // (CombSubSuperFast then divides by the summed squared window, as torch.istft does).  The reference materialises
 // [B,F+1,win/2+1] complex spectra four times; here one workgroup walks a run of consecutive frame PAIRS of one
 // utterance and nothing but the controls, the two input signals and the output touches HBM:
@@ -173,11 +174,8 @@ __global__ void __launch_bounds__(256) k_fast_combtooth4(const float* __restrict
 // ------------------------------------------------------------------------------------------------
 // the spectral filter itself
 // ------------------------------------------------------------------------------------------------
-// (cos, sin) of pi * p on v_cos_f32 / v_sin_f32, which take revolutions; fract keeps the argument in their range
-__device__ __forceinline__ f32x2 cis_pi(float p) {
-  const float rev = __builtin_amdgcn_fractf(0.5f * p);
-  return f32x2{__builtin_amdgcn_cosf(rev), __builtin_amdgcn_sinf(rev)};
-}
+// The filters' phase factor is cis_pi (ddsp_common.h): (cos, sin) of the float32 product fl32(pi32 * phase), the angle the
+// reference's complex64 exponential sees, in the forward and in the backward kernel alike.
 struct StftGeom {
   int F, T;               // control frames, samples per utterance (F * hop)
   int pairs;              // frame pairs per utterance: ceil((F + 1) / 2)   (frames 0..F)

@@ -678,9 +678,12 @@ def stft_filter(exciter, noise, harmonic_magnitude, harmonic_phase, noise_magnit
     nm, ldnm = _rows(noise_magnitude, n)
     npz, ldnp = (None, 0) if noise_phase is None else _rows(noise_phase, n)
     out = torch.empty(B, T, dtype=torch.float32, device=exciter.device)
+    # contiguous copies, where one had to be made, stay referenced until the call is enqueued: a temporary inside the argument
+    # list is released as soon as its pointer is taken
+    exc, nz, w = _f32c(exciter), _f32c(noise), _f32c(window)
     _ffi.check(_ffi.lib().ddsp_hip_stft_filter(
-        ptr(_f32c(exciter)), ptr(_f32c(noise)), int(noise_is_u01), ptr(hm), ldhm, ptr(hp), ldhp, ptr(nm), ldnm,
-        ptr(npz), ldnp, float(noise_scale), ptr(_f32c(window)), win, int(pad_reflect), int(normalize), B, F, hop,
+        ptr(exc), ptr(nz), int(noise_is_u01), ptr(hm), ldhm, ptr(hp), ldhp, ptr(nm), ldnm,
+        ptr(npz), ldnp, float(noise_scale), ptr(w), win, int(pad_reflect), int(normalize), B, F, hop,
         ptr(out), _ffi.stream_of(exciter)))
     return out
 
@@ -703,10 +706,12 @@ def stft_filter_backward(grad_signal, exciter, noise, harmonic_magnitude, harmon
     dev = exciter.device
     d_hm, d_hp, d_nm = (torch.empty(B, F, n, dtype=torch.float32, device=dev) for _ in range(3))
     d_np = None if noise_phase is None else torch.empty(B, F, n, dtype=torch.float32, device=dev)
+    # as in stft_filter: a copy made here (a strided cotangent, say) must outlive the argument list
+    exc, nz, w, grad = _f32c(exciter), _f32c(noise), _f32c(window), _f32c(grad_signal.reshape(B, T))
     _ffi.check(_ffi.lib().ddsp_hip_stft_filter_backward(
-        ptr(_f32c(exciter)), ptr(_f32c(noise)), int(noise_is_u01), ptr(hm), ldhm, ptr(hp), ldhp, ptr(nm), ldnm,
-        ptr(npz), ldnp, float(noise_scale), ptr(_f32c(window)), win, int(pad_reflect), int(normalize),
-        ptr(_f32c(grad_signal.reshape(B, T))), B, F, hop, ptr(d_hm), ptr(d_hp), ptr(d_nm), ptr(d_np),
+        ptr(exc), ptr(nz), int(noise_is_u01), ptr(hm), ldhm, ptr(hp), ldhp, ptr(nm), ldnm,
+        ptr(npz), ldnp, float(noise_scale), ptr(w), win, int(pad_reflect), int(normalize),
+        ptr(grad), B, F, hop, ptr(d_hm), ptr(d_hp), ptr(d_nm), ptr(d_np),
         _ffi.stream_of(exciter)))
     return d_hm, d_hp, d_nm, d_np
 
@@ -759,9 +764,10 @@ def combsubfast_synth(f0_frames, state: PhaseState, harmonic_magnitude, harmonic
     dev = f0.device
     ws, need = _stft_ws(B, F, hop, dev)
     signal = torch.empty(B, T, dtype=torch.float32, device=dev)
+    w = _f32c(window)                                           # held across the call (see stft_filter)
     _ffi.check(_ffi.lib().ddsp_hip_combsubfast_synth(
         ptr(f0), ptr(state.initial_phase), ptr(state.phase0), ptr(hm), ldhm, ptr(hp), ldhp, ptr(nm), ldnm,
-        ptr(nz), int(noise_is_u01), ptr(_f32c(window)), B, F, hop, float(sampling_rate), int(state.infer),
+        ptr(nz), int(noise_is_u01), ptr(w), B, F, hop, float(sampling_rate), int(state.infer),
         ptr(signal), ptr(ws), need, _ffi.stream_of(f0)))
     return signal
 
@@ -791,9 +797,10 @@ def combsubsuperfast_synth(f0_frames, state: FastSourceState, harmonic_magnitude
     dev = f0.device
     ws, need = _stft_ws(B, F, hop, dev)
     signal = torch.empty(B, T, dtype=torch.float32, device=dev)
+    w = _f32c(window)                                           # held across the call (see stft_filter)
     _ffi.check(_ffi.lib().ddsp_hip_combsubsuperfast_synth(
         ptr(f0), ptr(state.rad_acc), ptr(hm), ldhm, ptr(hp), ldhp, ptr(nm), ldnm, ptr(npz), ldnp, ptr(nz),
-        ptr(_f32c(window)), win, B, F, hop, float(sampling_rate), ptr(signal), ptr(ws), need, _ffi.stream_of(f0)))
+        ptr(w), win, B, F, hop, float(sampling_rate), ptr(signal), ptr(ws), need, _ffi.stream_of(f0)))
     return signal
 
 

@@ -194,6 +194,8 @@ __global__ void k_math(int fn, const float* a, const float* b, float* out, long 
       case 4: r = ddsp::sin_turns2(f32x2{a[i], b[i]}).y; break;
       case 5: r = ddsp::sinc_f32(a[i]); break;
       case 6: r = ddsp::div_pos(a[i], b[i]); break;
+      case 7: r = ddsp::cis_pi(a[i]).x; break;
+      case 8: r = ddsp::cis_pi(a[i]).y; break;
       default: break;
     }
     out[i] = r;

@@ -114,7 +114,8 @@ def test_wave_max_dpp_unsigned(units, waves_per_block):
 
 
 # ---------------------------------------------------------------- hardware-math wrappers
-FN = {"tanh_hw": 0, "exp_hw": 1, "sin_turns": 2, "sin_turns2.x": 3, "sin_turns2.y": 4, "sinc_f32": 5, "div_pos": 6}
+FN = {"tanh_hw": 0, "exp_hw": 1, "sin_turns": 2, "sin_turns2.x": 3, "sin_turns2.y": 4, "sinc_f32": 5, "div_pos": 6, "cis_pi.x": 7,
+      "cis_pi.y": 8}
 
 
 def _math(units, fn, a, b=None):
@@ -188,6 +189,19 @@ def test_sin_turns(units):
         assert err <= 3.9e-7
     assert np.array_equal(_bits(_math(units, "sin_turns2.x", a, b)), _bits(one_a))
     assert np.array_equal(_bits(_math(units, "sin_turns2.y", a, b)), _bits(one_b))
+
+
+@both
+def test_cis_pi(units):
+    """the spectral filters' phase factor: (cos, sin) of the float32 product fl32(pi32 * p), the angle the reference's complex64
+    exponential sees, for |pi p| <= 805, i.e. |p| <= 256 -- sin_turns' reduction and range, so sin_turns' bound: 3.9e-7 absolute"""
+    n, rng = _points(units), np.random.default_rng(17)
+    p = rng.uniform(-256, 256, n).astype(np.float32)
+    ang = (np.float32(np.pi) * p).astype(np.float32).astype(np.float64)
+    for fn, ref in (("cis_pi.x", np.cos(ang)), ("cis_pi.y", np.sin(ang))):
+        err = np.abs(_math(units, fn, p) - ref).max()
+        print("%s: worst abs error %.3e over %d points" % (fn, err, n))
+        assert err <= 3.9e-7
 
 
 @both

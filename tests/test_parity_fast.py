@@ -15,6 +15,7 @@ import torch
 
 from oracle import ddsp_oracle as O
 from tests.backends import BACKENDS, dev  # noqa: F401
+from tests.stft_oracle import _filter_case, _oracle_filter, hann
 
 SR, HOP = 44100, 512
 
@@ -29,10 +30,6 @@ def T_(a, device):
 
 def N_(t):
     return t.detach().cpu().numpy()
-
-
-def hann(win):
-    return (0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(win) / win)).astype(np.float32)
 
 
 @pytest.mark.parametrize("dev", BACKENDS, indirect=True)
@@ -58,35 +55,6 @@ def test_fast_source_shapes(dev, B, F, hop):
     assert np.array_equal(N_(st.rad_acc), ra)
     assert np.array_equal(N_(st.phase_frames)[..., 0], pf)
     assert np.abs(N_(st.combtooth) - comb).max() <= 3e-7
-
-
-def _filter_case(B, F, win, seed, noise_phase=True):
-    rng = np.random.default_rng(seed)
-    n = win // 2 + 1
-    T = F * HOP
-    exc = rng.standard_normal((B, T)).astype(np.float32)
-    nz = rng.standard_normal((B, T)).astype(np.float32)
-    hm, hp, nm, nph = [(s * rng.standard_normal((B, F, n))).astype(np.float32) for s in (1.0, 1.5, 1.0, 1.5)]
-    return exc, nz, hm, hp, nm, (nph if noise_phase else None)
-
-
-def _oracle_filter(exc, nz, hm, hp, nm, nph, win, w, reflect, normalize):
-    Hs = O.spectral_filters(hm, hp)
-    Hn = O.spectral_filters(nm, nph, 1.0 / 128.0)
-    mode = "reflect" if reflect else "constant"
-    w64 = w.astype(np.float64)
-    spec = np.fft.rfft(O._frames(exc, win, HOP, mode) * w64, win) * Hs + \
-        np.fft.rfft(O._frames(nz, win, HOP, mode) * w64, win) * Hn
-    fr = np.fft.irfft(spec, win) * w64
-    B, nfr, _ = fr.shape
-    total = win + HOP * (nfr - 1)
-    ola = np.zeros((B, total))
-    env = np.zeros(total)
-    for j in range(nfr):
-        ola[:, j * HOP:j * HOP + win] += fr[:, j]
-        env[j * HOP:j * HOP + win] += w64 * w64
-    sl = slice(win // 2, win // 2 + HOP * (nfr - 1))
-    return ola[:, sl] / env[sl] if normalize else ola[:, sl]
 
 
 @pytest.mark.parametrize("dev", BACKENDS, indirect=True)

@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """Time k_stft_filter variants on the MI355X (events on the launch stream): occupancy variant x run length,
-for the CombSubSuperFast (win 2048) and CombSubFast (win 1024) geometries at B=32 x 10 s."""
+for the CombSubSuperFast (win 2048) and CombSubFast (win 1024) geometries at B=32 x 10 s; BWD=1 adds k_stft_filter_bwd at the same
+variants.  REPS: timed calls per figure (default 10).  DDSP_HIP_LIB picks another build of the library (same-box A/B)."""
 import json
 import os
 import sys
@@ -8,12 +9,12 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
-from ddsp_svc_amd import synth
+from ddsp_svc_amd import _ffi, synth
 
 HOP = 512
 
 
-def timeit(fn, reps=10, warm=2):
+def timeit(fn, reps=int(os.environ.get("REPS", 10)), warm=2):
     for _ in range(warm):
         fn()
     torch.cuda.synchronize()
@@ -49,6 +50,11 @@ def main():
                 ms = timeit(lambda: synth.stft_filter(exc, nz, hm, hp, nm, nph if win == 2048 else None, w, HOP,
                                                       pad_reflect=True, normalize=True))
                 res["win%d_wps%d_run%s_ms" % (win, occ, run)] = round(ms, 4)
+                if os.environ.get("BWD") == "1":
+                    R = exc
+                    ms = timeit(lambda: synth.stft_filter_backward(R, exc, nz, hm, hp, nm, nph if win == 2048 else None, w, HOP,
+                                                                   pad_reflect=True, normalize=True))
+                    res["win%d_wps%d_run%s_bwd_ms" % (win, occ, run)] = round(ms, 4)
     print(json.dumps(res, indent=1))
 
 
